@@ -26,12 +26,18 @@ by more containers (weak scaling, configs 2-3):
               sketches merged by one reduce-scatter, rank error vs the exact path reported
 Data are generated on the device by krr_synth_fill_global (counter hash; no host packing, no PCIe).
 
-Prints ONE JSON line on rank 0 (contract in the task brief): value = containers of ALL
-ranks / max-over-ranks step time; roofline = the fused kernel's algorithmic
-bytes / its average launch time (HIP events on the launch stream) against 8 TB/s;
+Prints ONE JSON line on rank 0: value = containers of ALL ranks / max-over-ranks step
+time; ms_per_step = that step time; roofline = the fused kernel's algorithmic
+bytes / its average launch time (HIP events on the launch stream) against 8 TB/s.
+
+A plain run does only that: set-up, --warmup steps, --steps timed steps, the line.
+--dump-outputs DIR also writes the last timed step's results (DIR/<name>.npy, float64; the
+inputs depend on the arguments alone, so two builds can be compared array for array).
+--full adds, after the timed steps, everything else the line can report:
 cpu_baseline = the C oracle (OpenMP, the lease's cores) on a bounded sample copied from
 the device (N = 1); parity_vs_oracle_on_sample = this run's results (N > 1: the records
-gathered to rank 0) against the oracle on a sample regenerated from every shard.
+gathered to rank 0) against the oracle on a sample regenerated from every shard; the
+right-size, host-path and config-4 legs (config 5: the parity / rank-error sample).
 """
 from __future__ import annotations
 
@@ -64,6 +70,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline figure: parity with the "
+                         "oracle, the CPU baselines, right-sizing, the host path, the config-4 leg (config 5: the "
+                         "parity / rank-error sample and the CPU baseline).  A plain run sets up, warms up, times "
+                         "--steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0: the result arrays and "
+                         "the records on the host) as DIR/<name>.npy, float64, at most 64 MB in all (larger "
+                         "outputs: a fixed seeded sample of the rows, the same for every array)")
     ap.add_argument("--sketch-bits", type=int, default=5, help="config 5: log-linear bins per octave = 2^bits")
     ap.add_argument("--sketch-only", action="store_true",
                     help="config 5: stop at the sketch answer (approximate) instead of the exact refinement")
@@ -269,6 +284,29 @@ class _gc_timer:
 
         gc.callbacks.remove(self._cb)
         return {f"gen{g}": [self.n[g], round(self.t[g], 5)] for g in sorted(self.t)}
+
+
+DUMP_BUDGET = 64_000_000  # bytes of --dump-outputs files in all
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array of `arrays` (name -> 1-D host array, one row per container
+    or series) as path/<name>.npy in float64.  Past DUMP_BUDGET bytes in all, each array keeps
+    the same seeded sample of its rows (sorted; the row numbers written as rows_<length>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    # the row numbers beside them: at most two lengths (a rank's own results, all ranks' records)
+    per = (DUMP_BUDGET - 128 * (len(arrays) + 2)) // (8 * (len(arrays) + 2))
+    picks: dict = {}
+    for name, a in arrays.items():
+        n = a.shape[0]
+        if n > per:
+            if n not in picks:
+                picks[n] = np.sort(np.random.default_rng(20240).choice(n, size=per, replace=False))
+            a = a[picks[n]]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    for n, rows in picks.items():
+        np.save(os.path.join(path, f"rows_{n}.npy"), rows.astype(np.float64))
 
 
 def cgroup_cpu() -> dict:
@@ -768,7 +806,17 @@ def main():
         result["gather_mode_requested"] = args.gather
         result["gather_mode_used"] = gather_mode
         result["rccl_comm"] = rccl_info
-    if zero_copy or (dist_on and rank == 0 and not args.separate):
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results as its caller holds them: this rank's arrays in HBM and
+        # every rank's 32-B records on the host
+        from krr_amd.core.distributed import unpack_records
+
+        phase("dump outputs")
+        arrays = {k: v.cpu().numpy() for k, v in out.items()}
+        arrays.update({"records_" + k: v for k, v in unpack_records(host_rec[:containers_total].numpy()).items()})
+        dump_outputs(args.dump_outputs, arrays)
+    full = args.full
+    if full and (zero_copy or (dist_on and rank == 0 and not args.separate)):
         # the host buffer holds exactly what the launch computed (after the last step's sync);
         # N > 1: rank 0's own shard leads the gathered records
         ctx.pack_records(out, dev_rec, stream)
@@ -786,7 +834,7 @@ def main():
         pass
 
     # parity of this very run on a sample + the CPU baseline (rank 0, N = 1 only)
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if full and rank == 0 and not args.no_cpu_baseline and world == 1:
         from oracle import oracle
 
         m = S if args.cpu_sample <= 0 else max(1, min(args.cpu_sample, S))
@@ -854,13 +902,13 @@ def main():
             "source": "carried constant from BASELINE.md (SimpleStrategy.run + _format_result, config 1, "
                       "measured once in the build container; the reference cannot travel to the GPU box)"}
 
-    if rank == 0:
+    if full and rank == 0:
         phase("right-size")
         result.update(right_size(args, host_rec[:containers_total].numpy()))
-    if rank == 0 and world == 1 and not args.no_host_path and not args.sharded_host_path:
+    if full and rank == 0 and world == 1 and not args.no_host_path and not args.sharded_host_path:
         phase("host path")
         result.update(host_path(args, dev, c_host_sample=parts[0][2], objects=args.host_objects))
-    if args.c4_containers > 0 and args.config == 2:
+    if full and args.c4_containers > 0 and args.config == 2:
         phase("config-4 leg")
         del parts, out
         torch.cuda.empty_cache()
@@ -868,7 +916,7 @@ def main():
                           comm if gather_mode == "stream" else None, params)
         if rank == 0:
             result.update(leg)
-    if (world > 1 or args.sharded_host_path) and dist_on and not args.no_host_path:
+    if full and (world > 1 or args.sharded_host_path) and dist_on and not args.no_host_path:
         phase("host path (sharded)")
         hp = host_path_sharded(args, dev, world, rank, coll_dev, objects=args.host_objects)
         if rank == 0:
@@ -877,7 +925,7 @@ def main():
         result["config"]["backend"] = backend
         if backend != "nccl":
             result["config"]["ranks_share_gpus"] = f"{world} ranks on {ndev} GPU(s) (gloo rehearsal)"
-        if rank == 0:
+        if full and rank == 0:
             result.update(parity_gathered(args, ctx, dev, world, params, host_rec, gaps, pod_len, seed))
     if rank == 0:
         print(json.dumps(result), file=_JSON_OUT, flush=True)
@@ -1911,6 +1959,24 @@ def run_config5(args, world, rank, local, dev, coll_dev):
             result["roofline_tail"]["traffic_source"] = tr[tkey].get("source")
     except (OSError, ValueError):
         pass
+    if args.dump_outputs and rank == 0:
+        # the last timed step's answers as rank 0's host holds them (config-5 records: value
+        # bits, count | flags << 48, 0, 0)
+        phase("dump outputs")
+        rec = host_rec[:S].numpy()
+        dump_outputs(args.dump_outputs, {"value": rec[:, 0].copy().view(np.float64),
+                                         "count": rec[:, 1] & ((1 << 48) - 1), "flags": rec[:, 1] >> 48})
+
+    def close():
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        ctx.close()
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), file=_JSON_OUT, flush=True)
+        return close()
     # parity / rank error on a sample of series, regathered whole on rank 0
     phase("parity")
     m = max(1, min(args.error_sample, S))
@@ -2042,10 +2108,7 @@ def run_config5(args, world, rank, local, dev, coll_dev):
                                                             and np.array_equal(recs[:, 1] & ((1 << 48) - 1), on))
                 result["parity_oracle_sample_series"] = cs
         print(json.dumps(result), file=_JSON_OUT, flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
-    ctx.close()
+    close()
 
 
 def params_mode(args) -> str:

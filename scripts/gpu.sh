@@ -4,8 +4,8 @@
 # steps:
 #   tests        pytest -m gpu (one process, per-test timeout) + smoke()
 #   tests:EXPR   only the GPU tests matching -k EXPR
-#   bench        bench.py default (config 2, linear p99) -> bench.json
-#   bench:ARGS   bench.py with ARGS (commas for spaces), e.g. bench:--config,3
+#   bench        bench.py --full, default workload (config 2, linear p99) -> bench.json
+#   bench:ARGS   bench.py --full with ARGS (commas for spaces), e.g. bench:--config,3
 #   prof         rocprofv3 --kernel-trace --stats of the default bench -> kernel_stats.csv
 #   prof:ARGS    the same for bench.py ARGS
 #   pmc          FETCH_SIZE / WRITE_SIZE passes of the default bench (separate runs)
@@ -48,7 +48,7 @@ for step in "$@"; do
       fi
       ;;
     bench)
-      timeout -k 10 600 python -u bench.py $args > "$OUT/bench${n:+_$n}.json" 2> "$OUT/bench${n:+_$n}.err" \
+      timeout -k 10 600 python -u bench.py --full $args > "$OUT/bench${n:+_$n}.json" 2> "$OUT/bench${n:+_$n}.err" \
         || { echo "bench $args failed"; tail -20 "$OUT/bench${n:+_$n}.err"; exit 1; }
       python - "$OUT/bench${n:+_$n}.json" "$args" <<'EOF'
 import json, sys

@@ -35,8 +35,8 @@ def test_sharded_runner_two_ranks_on_gpu(entry, path, tmp_path):
 
 def _bench(args, timeout=240):
     env = dict(os.environ, KRR_BENCH_BACKEND="gloo")
-    p = subprocess.run(["timeout", "-k", "10", str(timeout), sys.executable, os.path.join(ROOT, "bench.py"), *args],
-                       capture_output=True, text=True, env=env, timeout=timeout + 30)
+    p = subprocess.run(["timeout", "-k", "10", str(timeout), sys.executable, os.path.join(ROOT, "bench.py"), "--full",
+                        *args], capture_output=True, text=True, env=env, timeout=timeout + 30)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -66,7 +66,7 @@ def test_bench_under_torchrun_like_the_driver():
     env.pop("KRR_BENCH_LAUNCHED", None)
     p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--containers", "400", "--steps", "2",
+                        os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--containers", "400", "--steps", "2",
                         "--warmup", "1", "--parity-block", "64", "--deadline", "200"],
                        capture_output=True, text=True, env=env, timeout=270)
     assert p.returncode == 0, p.stderr[-4000:]
@@ -96,7 +96,8 @@ def test_bench_rccl_path_one_rank(gather, comm):
                MASTER_PORT=str(port), KRR_BENCH_BACKEND="nccl")
     p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist",
                         "--containers", "400", "--steps", "5", "--warmup", "2", "--gather", gather,
-                        "--comm", comm, "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=270)
+                        "--comm", comm, "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
+                       timeout=270)
     assert p.returncode == 0, p.stderr[-4000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert r["n_gpus"] == 1 and r["config"]["records"] == "HBM + RCCL gather to rank 0"
@@ -136,7 +137,7 @@ def test_bench_config5_window_refine_one_rank():
     oracle on the CPU-baseline sample and k_select on the error sample."""
     p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(ROOT, "bench.py"), "--config", "5",
                         "--containers", "800", "--c5-refine", "--steps", "2", "--warmup", "1", "--error-sample", "300",
-                        "--cpu-sample", "100"], capture_output=True, text=True, timeout=270)
+                        "--full", "--cpu-sample", "100"], capture_output=True, text=True, timeout=270)
     assert p.returncode == 0, p.stderr[-4000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert r["config"]["method"] == "window" and r["parity_vs_single_window_select"] is True, r
@@ -372,7 +373,7 @@ def test_bench_chunked_fleet_one_rank(args):
     chunk written into the host buffer): parity with the oracle on every container and the
     host records equal to the device results."""
     p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(ROOT, "bench.py"), *args,
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=270)
+                        "--full", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=270)
     assert p.returncode == 0, p.stderr[-4000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert r["launches_per_step"] > 1 and r["parity_vs_oracle_on_sample"] is True, r
@@ -386,7 +387,8 @@ def test_bench_config5_direct_chunked():
     select over the regathered series."""
     p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(ROOT, "bench.py"), "--config", "5",
                         "--containers", "600", "--c5-chunk-gib", "0.2", "--steps", "2", "--warmup", "1",
-                        "--error-sample", "600", "--no-cpu-baseline"], capture_output=True, text=True, timeout=270)
+                        "--error-sample", "600", "--full", "--no-cpu-baseline"], capture_output=True, text=True,
+                       timeout=270)
     assert p.returncode == 0, p.stderr[-4000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert r["parity_vs_single_window_select"] is True and r["parity_sample_series"] == 600, r
@@ -398,7 +400,8 @@ def test_bench_config5_direct_oracle_parity():
     equal the oracle (parity_vs_oracle_on_sample), beside the k_select check."""
     p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(ROOT, "bench.py"), "--config", "5",
                         "--containers", "700", "--c5-chunk-gib", "0.3", "--steps", "2", "--warmup", "1",
-                        "--error-sample", "200", "--cpu-sample", "60"], capture_output=True, text=True, timeout=270)
+                        "--error-sample", "200", "--full", "--cpu-sample", "60"], capture_output=True, text=True,
+                       timeout=270)
     assert p.returncode == 0, p.stderr[-4000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     assert r["parity_vs_oracle_on_sample"] is True and r["parity_oracle_sample_series"] == 300, r
@@ -458,7 +461,7 @@ def test_bench_rccl_one_rank_config4_leg_and_sharded_host_path():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(port), KRR_BENCH_BACKEND="nccl")
     p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist",
-                        "--containers", "400", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                        "--containers", "400", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--c4-containers", "5000", "--c4-steps", "2", "--chunk-gib", "0.1", "--sharded-host-path",
                         "--host-objects", "200"], capture_output=True, text=True, env=env, timeout=270)
     assert p.returncode == 0, p.stderr[-4000:]
@@ -466,3 +469,38 @@ def test_bench_rccl_one_rank_config4_leg_and_sharded_host_path():
     assert r["config4_parity_vs_oracle_on_sample"] is True and r["config4_parity_gathered_vs_rank0_kernel"] is True
     assert r["config4_definition"].find("RCCL gather") >= 0 and r["config4_gather_ms_max"] >= 0
     assert r["e2e_sharded_equals_host_parse"] is True and len(r["e2e_per_rank_s"]) == 1
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run stops at the headline (no parity, baseline, right-size, host-path or config-4
+    keys), times exactly --steps steps, and --dump-outputs writes the last step's results: the
+    same arrays from a plain and a --full run of the same arguments, the --full one checked
+    against the oracle on every container; the host records hold what the device arrays do."""
+    def run(name, *extra):
+        d = str(tmp_path / name)
+        p = subprocess.run(["timeout", "-k", "10", "240", sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                            "--containers", "400", "--steps", "3", "--warmup", "1", "--dump-outputs", d, *extra],
+                           capture_output=True, text=True, timeout=270)
+        assert p.returncode == 0, p.stderr[-4000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+    r, a = run("plain")
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["dtype"] == "f64"
+    assert r["value"] == pytest.approx(400 / (r["ms_per_step"] * 1e-3))
+    moved = ("parity_vs_oracle_on_sample", "records_host_equal_device", "cpu_baseline", "cpu_baseline_numpy",
+             "round_objects_per_s", "e2e_objects_per_s", "config4_containers_per_s")
+    assert not [k for k in moved if k in r]
+    keys = ("cpu_value", "cpu_count", "cpu_flags", "mem_value", "mem_count", "mem_flags")
+    assert sorted(a) == sorted([*keys, *("records_" + k for k in keys)])
+    for k in keys:
+        assert a[k].dtype == np.float64 and a[k].shape == (400,)
+        assert np.array_equal(a[k].view(np.uint64), a["records_" + k].view(np.uint64)), k
+    assert (a["cpu_count"] > 0).all() and (a["cpu_value"] > 0).all() and (a["mem_value"] > 1e8).all()
+    f, b = run("full", "--full", "--no-host-path", "--c4-containers", "0", "--numpy-seconds", "0.2")
+    assert f["parity_vs_oracle_on_sample"] is True and f["parity_sample_containers"] == 400
+    assert f["records_host_equal_device"] is True and "round_objects_per_s" in f
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert np.array_equal(a[k].view(np.uint64), b[k].view(np.uint64)), k
