@@ -241,6 +241,41 @@ typedef struct {
 
 int krr_select_plan(int64_t max_segment_len, const krr_percentile_params* params, krr_select_plan_info* out);
 
+/* ---- Several CPU percentiles from one pass (simple_limit: request and limit; p50/p95/p99
+ * profiles) ----
+ * params[0 .. n_params): 1 <= n_params <= KRR_MAX_PERCENTILES entries of one `mode`, each with
+ * its own p_num / p_den / q / k_table (checked per entry as for one percentile); duplicates are
+ * allowed.  Percentile j's values and flags land at out_value[j * S + s] / out_flags[j * S + s]
+ * and equal, bit for bit, what krr_segmented_percentile (krr_simple_run) writes for params[j]
+ * alone; out_count[s] is shared.  The memory outputs equal krr_simple_run's.
+ *
+ * Shared path: SORTED_LOWER / LINEAR stream every CPU segment ONCE into a candidate buffer
+ * sized for the innermost percentile (the final rank queries only read it), when that buffer
+ * fits the single pass (krr_multi_plan: shared == 1); REF_INDEX counts the present samples once
+ * and then locates every position (always shared).  Otherwise (mid percentiles of long series)
+ * the existing per-percentile launches run: one rides the fused launch with the memory half,
+ * the others are krr_segmented_percentile passes — identical results. */
+#define KRR_MAX_PERCENTILES 4
+
+typedef struct {
+    int32_t shared;    /* 1: one pass over the CPU values answers every percentile */
+    int32_t bottom;    /* shared: 1 when the smallest keys are kept */
+    int64_t tkeep;     /* shared: keys a segment of max length must keep (0 for REF_INDEX) */
+    int64_t cap_keys;  /* shared: single-pass candidate capacity (0 for REF_INDEX) */
+    int64_t lds_bytes; /* shared: dynamic LDS per workgroup (0 for REF_INDEX) */
+} krr_multi_plan_info;
+
+/* Host only, like krr_select_plan. */
+int krr_multi_plan(int64_t max_segment_len, const krr_percentile_params* params, int32_t n_params,
+                   krr_multi_plan_info* out);
+int krr_segmented_percentiles(krr_ctx* ctx, const krr_series* series, const krr_percentile_params* params,
+                              int32_t n_params, double* out_value /* [P*S] */, int64_t* out_count /* [S] */,
+                              uint32_t* out_flags /* [P*S] */, void* stream);
+int krr_simple_run_multi(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,
+                         const krr_percentile_params* params, int32_t n_params, double* cpu_value /* [P*S] */,
+                         int64_t* cpu_count /* [S] */, uint32_t* cpu_flags /* [P*S] */, double* mem_value,
+                         int64_t* mem_count, uint32_t* mem_flags, void* stream);
+
 /* Counters of the ctx since krr_create (synchronises the device): segments whose
  * one-pass window select (wselect) missed and were finished by the two-pass
  * histogram select.  Diagnostic: results are exact either way. */

@@ -86,6 +86,9 @@ EXPORTED_SYMBOLS = (
     "krr_window_export",
     "krr_window_merge",
     "krr_select_plan",
+    "krr_multi_plan",
+    "krr_segmented_percentiles",
+    "krr_simple_run_multi",
     "krr_get_stats",
     "krr_comm_unique_id",
     "krr_comm_init",
@@ -223,6 +226,20 @@ class KrrSelectPlanInfo(ctypes.Structure):
     ]
 
 
+KRR_MAX_PERCENTILES = 4
+
+
+class KrrMultiPlanInfo(ctypes.Structure):
+    """include/krr_amd.h krr_multi_plan_info (32 bytes)."""
+    _fields_ = [
+        ("shared", ctypes.c_int32),
+        ("bottom", ctypes.c_int32),
+        ("tkeep", ctypes.c_int64),
+        ("cap_keys", ctypes.c_int64),
+        ("lds_bytes", ctypes.c_int64),
+    ]
+
+
 class KrrJsonBodies(ctypes.Structure):
     """include/krr_amd.h krr_json_bodies."""
     _fields_ = [
@@ -288,6 +305,12 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_synth_fill_global.restype = ctypes.c_int
         lib.krr_select_plan.argtypes = [i64, pp, ctypes.POINTER(KrrSelectPlanInfo)]
         lib.krr_select_plan.restype = ctypes.c_int
+        lib.krr_multi_plan.argtypes = [i64, pp, i32, ctypes.POINTER(KrrMultiPlanInfo)]
+        lib.krr_multi_plan.restype = ctypes.c_int
+        lib.krr_segmented_percentiles.argtypes = [vp, sp, pp, i32, vp, vp, vp, vp]
+        lib.krr_segmented_percentiles.restype = ctypes.c_int
+        lib.krr_simple_run_multi.argtypes = [vp, sp, sp, pp, i32, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_simple_run_multi.restype = ctypes.c_int
         lib.krr_get_stats.argtypes = [vp, ctypes.POINTER(i64)]
         lib.krr_get_stats.restype = ctypes.c_int
         lib.krr_comm_unique_id.argtypes = [vp, vp]
@@ -477,6 +500,44 @@ class Context:
             out["cpu_value"].data_ptr(), out["cpu_count"].data_ptr(), out["cpu_flags"].data_ptr(),
             out["mem_value"].data_ptr(), out["mem_count"].data_ptr(), out["mem_flags"].data_ptr(),
             records.data_ptr() if records is not None else None, fsrc, fdst, fbytes, self._stream(stream)))
+
+    def _param_array(self, params_list, *series: KrrSeries):
+        """The krr_percentile_params array of a percentile set, each entry's index table bound
+        as ``_bound`` does (the array keeps the bound entries, and so their tables, alive)."""
+        bound = [self._bound(p, *series) for p in params_list]
+        arr = (KrrPercentileParams * len(bound))()
+        for j, p in enumerate(bound):
+            arr[j] = KrrPercentileParams(p.mode, p.reserved, p.p_num, p.p_den, p.q, p.k_table, p.k_table_len)
+        arr._keep = bound
+        return arr
+
+    def segmented_percentiles(self, series: KrrSeries, params_list, out_value, out_count, out_flags,
+                              stream=None) -> None:
+        """Several percentiles of every segment (krr_segmented_percentiles): out_value float64
+        [P, S] and out_flags int32 [P, S], row j for params_list[j]; out_count int64 [S].  One
+        pass over the values when the set shares a buffer (``multi_plan(...).shared``)."""
+        P, S = len(params_list), series.n_segments
+        _check_tensor(out_value, "float64", P * S)
+        _check_tensor(out_count, "int64", S)
+        _check_tensor(out_flags, "int32", P * S)
+        arr = self._param_array(params_list, series)
+        self._check(self._lib.krr_segmented_percentiles(
+            self._h, ctypes.byref(series), arr, P, out_value.data_ptr(), out_count.data_ptr(),
+            out_flags.data_ptr(), self._stream(stream)))
+
+    def simple_run_multi(self, cpu: KrrSeries, mem: KrrSeries, params_list, out: dict, stream=None) -> None:
+        """simple_run for several CPU percentiles (krr_simple_run_multi): out as for simple_run
+        with cpu_value float64 [P, S] and cpu_flags int32 [P, S], row j for params_list[j]."""
+        P, n = len(params_list), cpu.n_segments
+        for k, dt, m in (("cpu_value", "float64", P * n), ("cpu_count", "int64", n), ("cpu_flags", "int32", P * n),
+                         ("mem_value", "float64", n), ("mem_count", "int64", n), ("mem_flags", "int32", n)):
+            _check_tensor(out[k], dt, m)
+        arr = self._param_array(params_list, cpu)
+        self._check(self._lib.krr_simple_run_multi(
+            self._h, ctypes.byref(cpu), ctypes.byref(mem), arr, P,
+            out["cpu_value"].data_ptr(), out["cpu_count"].data_ptr(), out["cpu_flags"].data_ptr(),
+            out["mem_value"].data_ptr(), out["mem_count"].data_ptr(), out["mem_flags"].data_ptr(),
+            self._stream(stream)))
 
     def pack_records(self, out: dict, records, stream=None) -> None:
         """out: the six result tensors; records: int64 [S, 4] device tensor."""
@@ -867,6 +928,29 @@ def select_plan(max_segment_len: int, params: KrrPercentileParams) -> KrrSelectP
     rc = lib.krr_select_plan(int(max_segment_len), ctypes.byref(params), ctypes.byref(info))
     if rc != KRR_OK:
         raise NativeError(rc, "krr_select_plan")
+    return info
+
+
+def multi_plan(max_segment_len: int, params_list) -> KrrMultiPlanInfo:
+    """The path krr_segmented_percentiles / krr_simple_run_multi take for a percentile set when
+    the longest segment has max_segment_len slots (krr_multi_plan; host only): ``shared`` = 1
+    when one pass over the CPU values answers every percentile."""
+    lib = load_library()
+    keep = []
+    arr = (KrrPercentileParams * len(params_list))()
+    for j, p in enumerate(params_list):
+        rule = getattr(p, "rule", None)
+        tab_ptr, tab_len = p.k_table, p.k_table_len
+        if rule is not None and not p.k_table and p.mode != KRR_PCT_LINEAR and rule.needs_table(max_segment_len):
+            # the plan only needs to know a table is there (its wider margins); it reads no entry
+            tab = rule.table(max(int(max_segment_len), 1))
+            keep.append(tab)
+            tab_ptr, tab_len = tab.ctypes.data, tab.size
+        arr[j] = KrrPercentileParams(p.mode, p.reserved, p.p_num, p.p_den, p.q, tab_ptr, tab_len)
+    info = KrrMultiPlanInfo()
+    rc = lib.krr_multi_plan(int(max_segment_len), arr, len(params_list), ctypes.byref(info))
+    if rc != KRR_OK:
+        raise NativeError(rc, "krr_multi_plan: 1 to 4 percentiles of one mode")
     return info
 
 

@@ -172,13 +172,10 @@ class SimpleEngine:
         exactness class >= 1 (``_locate_chunk``); returns its answers, else None."""
         import torch
 
-        from krr_amd.core.distributed import fleet_shard_bounds, slice_fleet
+        from krr_amd.core.distributed import slice_fleet
 
         S = fleet.n_objects
-        nbytes = 8 * (int(fleet.cpu.offsets[-1]) + int(fleet.mem.offsets[-1]))
-        resident = isinstance(fleet.cpu.values, torch.Tensor) and fleet.cpu.values.is_cuda
-        n = 1 if resident or nbytes <= 2 * self.chunk_bytes else -(-nbytes // self.chunk_bytes)
-        bounds = [(0, S)] if n == 1 else [(lo, hi) for lo, hi in fleet_shard_bounds(fleet, n) if hi > lo]
+        bounds = self._chunk_bounds(fleet)
         ctx = self.context()
         dev = torch.device("cuda", self.device)
         out = {k: torch.empty(S, dtype=dt, device=dev) for k, dt in
@@ -196,6 +193,73 @@ class SimpleEngine:
             if locate:
                 self._locate_chunk(ctx, part, cs, ms, params, chunk_out, loc, lo)
         return loc
+
+    def _chunk_bounds(self, fleet: PackedFleet) -> list:
+        """The object ranges a fleet runs as: whole when it is resident in HBM or within two
+        chunks of values, else sample-balanced chunks of about ``chunk_bytes``."""
+        import torch
+
+        from krr_amd.core.distributed import fleet_shard_bounds
+
+        S = fleet.n_objects
+        nbytes = 8 * (int(fleet.cpu.offsets[-1]) + int(fleet.mem.offsets[-1]))
+        resident = isinstance(fleet.cpu.values, torch.Tensor) and fleet.cpu.values.is_cuda
+        n = 1 if resident or nbytes <= 2 * self.chunk_bytes else -(-nbytes // self.chunk_bytes)
+        return [(0, S)] if n == 1 else [(lo, hi) for lo, hi in fleet_shard_bounds(fleet, n) if hi > lo]
+
+    def run_packed_multi(self, fleet: PackedFleet, params_list) -> list:
+        """Several CPU percentiles of a fleet (host- or device-packed) from one fused pass per
+        chunk (krr_simple_run_multi): one RawResults per entry of ``params_list``, sharing the
+        memory arrays and the CPU counts, so ``krr_amd.core.exact.resolve`` and
+        ``cpu_from_raw`` work per percentile unchanged.  HistoryData segments of exactness
+        class >= 1 are located per percentile (``_locate_chunk``)."""
+        import torch
+
+        from krr_amd.core.distributed import slice_fleet
+
+        params_list = list(params_list)
+        if fleet.cpu.n_segments != fleet.mem.n_segments:
+            raise ValueError("cpu and memory need one segment per object each")
+        ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        S, P = fleet.n_objects, len(params_list)
+        if S == 0:
+            e = np.zeros(0)
+            return [RawResults(e, e.astype(np.int64), e.astype(np.uint32), e, e.astype(np.int64),
+                               e.astype(np.uint32)) for _ in range(P)]
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(self.device):
+            out = {k: torch.empty(shape, dtype=dt, device=dev) for k, dt, shape in
+                   (("cpu_value", torch.float64, (P, S)), ("cpu_count", torch.int64, (S,)),
+                    ("cpu_flags", torch.int32, (P, S)), ("mem_value", torch.float64, (S,)),
+                    ("mem_count", torch.int64, (S,)), ("mem_flags", torch.int32, (S,)))}
+            locs = [None] * P
+            for j, params in enumerate(params_list):
+                if needs_locate(fleet, params):
+                    locs[j] = {r: tuple(np.full(S, -1, dtype=np.int64) for _ in range(3)) for r in ("cpu", "mem")}
+            for lo, hi in self._chunk_bounds(fleet):
+                part = fleet if (lo, hi) == (0, S) else slice_fleet(fleet, lo, hi)
+                cv, co = self._to_device(part.cpu)
+                mv, mo = self._to_device(part.mem)
+                cs = ctx.series(cv, co, max(part.cpu.max_len, 1), part.cpu.gaps_are_nan)
+                ms = ctx.series(mv, mo, max(part.mem.max_len, 1), part.mem.gaps_are_nan)
+                n = hi - lo
+                whole = n == S
+                # a chunk's rows are not contiguous in the [P, S] outputs: its own [P, n] block
+                chunk = out if whole else {k: torch.empty((P, n) if v.dim() == 2 else (n,), dtype=v.dtype, device=dev)
+                                           for k, v in out.items()}
+                ctx.simple_run_multi(cs, ms, params_list, chunk)
+                if not whole:
+                    for k, v in out.items():
+                        v[..., lo:hi] = chunk[k]
+                for j, params in enumerate(params_list):
+                    if locs[j] is not None:
+                        one = dict(chunk, cpu_value=chunk["cpu_value"][j], cpu_flags=chunk["cpu_flags"][j])
+                        self._locate_chunk(ctx, part, cs, ms, params, one, locs[j], lo)
+            torch.cuda.current_stream(self.device).synchronize()
+        host = {k: v.cpu().numpy() for k, v in out.items()}
+        return [RawResults(host["cpu_value"][j], host["cpu_count"], host["cpu_flags"][j].view(np.uint32),
+                           host["mem_value"], host["mem_count"], host["mem_flags"].view(np.uint32), locs[j])
+                for j in range(P)]
 
     def _locate_chunk(self, ctx, part: PackedFleet, cs, ms, params, out: dict, loc: dict, lo: int) -> None:
         """krr_locate for the chunk's class >= 1 segments that select one sample: memory

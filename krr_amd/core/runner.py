@@ -79,6 +79,20 @@ class BatchedRunner:
         if not supports_packed(self.strategy):
             raise TypeError(f"{type(self.strategy).__name__} has no batched packed path; use recommend()")
 
+    def _packed_hook(self):
+        """A strategy's own ``allocations_from_packed(fleet, cpu_min, mem_min, model=, resource_type=)``
+        (simple_limit: two CPU values per object), or None: ``simple``'s shape (run_fleet +
+        krr_amd.core.fast_round, CPU limit None)."""
+        hook = getattr(self.strategy, "allocations_from_packed", None)
+        return hook if callable(hook) and supports_packed(self.strategy) else None
+
+    def _require_records(self) -> None:
+        """The sharded paths carry one 32-byte record per object: one CPU value."""
+        if self._packed_hook() is not None:
+            raise NotImplementedError(
+                f"{type(self.strategy).__name__} has no multi-GPU sharded path: the 32-byte result record holds "
+                "one CPU value; run it on one GPU")
+
     # --- multi-GPU: one process per GPU ------------------------------------------
     def recommend_shard(self, local_fleet, group=None, dst: int = 0, device: Optional[int] = None):
         """This rank's contiguous object shard -> ONE kernel pass (records written by the
@@ -95,6 +109,7 @@ class BatchedRunner:
         from krr_amd.core.distributed import record_counts, records_from_raw
 
         self._require_packed()
+        self._require_records()
         dev = local_device() if device is None else int(device)
         settings = self.strategy.settings
         coll = collective_device(group, dev)
@@ -149,6 +164,7 @@ class BatchedRunner:
 
         if parser not in ("device", "host", "hybrid"):
             raise ValueError("parser must be 'device', 'host' or 'hybrid'")
+        self._require_records()
         # ONE device for the pack and the kernel pass: this rank's GPU (LOCAL_RANK) unless
         # the caller names one — the packer's own default (settings.device) is GPU 0
         dev = local_device() if device is None else int(device)
@@ -165,6 +181,7 @@ class BatchedRunner:
     def recommend_packed_sharded(self, fleet, group=None, dst: int = 0, device: Optional[int] = None):
         """Every rank holds the same packed fleet: each runs its sample-balanced contiguous
         shard (``fleet_shard_bounds``) and ``dst`` receives the whole fleet's results."""
+        self._require_records()
         import torch.distributed as dist
 
         from krr_amd.core.distributed import fleet_shard_bounds, slice_fleet
@@ -184,6 +201,7 @@ class BatchedRunner:
         from krr_amd.core.distributed import shard_bounds
 
         self._require_packed()
+        self._require_records()
         lo, hi = shard_bounds([max(len(o.pods), 1) for o in objects],
                               dist.get_world_size(group))[dist.get_rank(group)]
         histories = await self.gather_histories(objects[lo:hi], loader)
@@ -199,6 +217,9 @@ class BatchedRunner:
         from krr_amd.core.fast_round import allocations_batch
 
         self._require_packed()
+        hook = self._packed_hook()
+        if hook is not None:
+            return hook(fleet, self.cpu_min_value, self.memory_min_value, model=model, resource_type=resource_type)
         raw = self.strategy.settings.run_fleet(fleet)
         return allocations_batch(raw, self.strategy.settings, self.cpu_min_value, self.memory_min_value, model=model,
                                  resource_type=resource_type)
@@ -212,6 +233,14 @@ class BatchedRunner:
         from krr_amd.core.fast_round import result_batch
 
         self._require_packed()
+        if self._packed_hook() is not None:  # the scan reads the allocations, both CPU values in them
+            from krr_amd.core.models.result import collect_result
+
+            if models is None:
+                return collect_result(objects, self.allocations_packed(fleet))
+            allocs = self.allocations_packed(fleet, model=models.ResourceAllocations,
+                                             resource_type=models.ResourceType)
+            return collect_result(objects, allocs, models)
         raw = self.strategy.settings.run_fleet(fleet)
         return result_batch(objects, raw, self.strategy.settings, self.cpu_min_value, self.memory_min_value,
                             threads=threads, models=models)
@@ -247,7 +276,8 @@ class BatchedRunner:
         ``"hybrid"``: both at once on disjoint object ranges (``pack_hybrid``), one kernel
         pass per range.  No Decimal lists either way; native rounding."""
         self._require_packed()
-        if parser == "hybrid":
+        # (a strategy with its own packed hook packs hybrid too, then runs one pass over the whole fleet)
+        if parser == "hybrid" and self._packed_hook() is None:
             import threading
 
             import torch

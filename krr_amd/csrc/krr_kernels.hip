@@ -2651,6 +2651,226 @@ __global__ __launch_bounds__(64, CPU_KIND == CPU_HSELECT ? window_waves(false)
     }
 }
 
+// ------------------------ SEVERAL PERCENTILES ------------------------------
+// krr_segmented_percentiles / krr_simple_run_multi: P <= KRR_MAX_PERCENTILES percentiles of
+// every CPU segment from ONE pass over its values.  SelectProc's final rank queries
+// (rank_key, rank_key_pair, kth_largest) only read the candidate buffer and write the
+// 64-key gather area, so a buffer holding the keys the innermost percentile needs
+// (plan_side_multi) answers every percentile outside it too; REF_INDEX on the gapped
+// layout counts the present samples once and then walks to each position.  Percentile
+// j's value and flags go to out_v / out_f[j * S + s]; the present count is shared.
+struct MultiArgs {
+    const double* vals;
+    const int64_t* offs;
+    int64_t S;
+    int32_t gaps;
+    int32_t remap;   // xcd_item: per-XCD segment ranges (KRR_XCD_REMAP_MAXLEN)
+    uint32_t cap;    // single-pass candidate capacity (keys) of the shared buffer
+    PctSet ps;
+    double* out_v;   // [P * S]
+    int64_t* out_n;  // [S]
+    uint32_t* out_f; // [P * S]
+};
+
+// The one-percentile arguments ranks_for / finish_value read, for percentile j of the set.
+__device__ __forceinline__ SelectArgs pct_args(const MultiArgs& A, int j) {
+    SelectArgs B{};
+    B.vals = A.vals;
+    B.offs = A.offs;
+    B.S = A.S;
+    B.mode = A.ps.mode;
+    B.gaps = A.gaps;
+    B.p_num = A.ps.p_num[j];
+    B.p_den = A.ps.p_den[j];
+    B.q = A.ps.q[j];
+    B.ktab = A.ps.ktab[j];
+    B.ktab_len = A.ps.ktab_len[j];
+    return B;
+}
+
+// select_segment_with for a set of percentiles: one SelectProc sized by the set's plan,
+// one stream, then the rank queries and finish_value once per percentile.
+template <class Streamer>
+__device__ __forceinline__ void select_segment_multi_with(const MultiArgs& A, int64_t s, unsigned char* smem,
+                                                          int lane, Streamer stream) {
+    const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    const int64_t L = end - beg;
+    const SidePlan sp = plan_side_multi(L, A.ps);
+    SelectProc P;
+    P.buf = reinterpret_cast<uint64_t*>(smem + kSelectLdsFixed);
+    P.H = reinterpret_cast<uint32_t*>(smem);
+    P.small = reinterpret_cast<uint64_t*>(smem + 1024);
+    P.lane = lane;
+    P.cap = A.cap;
+    P.tkeep = sp.tkeep;
+    P.tstop = A.cap - kChunkElems / 2;
+    P.flip = sp.bottom ? ~0ull : 0ull;
+    P.cnt = 0;
+    P.bad = 0;
+#ifdef KRR_DIAG
+    for (int d = 0; d < D_WORDS; ++d) P.diag[d] = 0;
+#endif
+    uint64_t thr0 = 0;  // inclusive at the lowest key: every sample is a candidate
+#if KRR_SELECT_PROBE
+    if (!sp.bottom && A.cap && select_probe_pays(L, sp.tkeep, A.cap)) thr0 = P.probe_threshold(A.vals, beg, L);
+#endif
+    uint32_t pad;
+    uint64_t nnan, n;
+#pragma unroll 1
+    for (;;) {
+        P.cnt = 0;
+        P.eqs = 0;
+        P.nnan_lane = 0;
+        P.bad = 0;
+        P.set_thr(thr0, 1u);
+        pad = stream(P);  // NaN padding slots
+        __syncthreads();
+        nnan = wave_sum_u32(P.nnan_lane) - pad;
+        n = A.gaps ? (uint64_t)L - nnan : (uint64_t)L;  // present samples
+        if (thr0 == 0 || n == 0 || (nnan && !A.gaps)) break;
+        // Speculative start: exact iff the LOWEST rank any percentile needs is held in buf
+        // (ranks below n - cnt - ties lie under thr0); else stream again from the lowest key.
+        const uint64_t ties = P.incl ? 0u : P.eqs;
+        int64_t rmin = (int64_t)n;
+#pragma unroll 1
+        for (int j = 0; j < A.ps.n; ++j) {
+            const int64_t r = ranks_for(pct_args(A, j), n).r0;
+            rmin = r < rmin ? r : rmin;
+        }
+        if (!P.bad && (uint64_t)rmin >= n - P.cnt - ties) break;
+        thr0 = 0;
+    }
+    uint64_t bmn = 0, bmx = 0;
+    if (P.cnt) P.buf_minmax(bmn, bmx);
+
+    const uint32_t base = n == 0 ? KRR_FLAG_EMPTY : (nnan && !A.gaps) ? KRR_FLAG_NAN : 0u;
+    const uint32_t bad_stream = P.bad;
+#pragma unroll 1
+    for (int j = 0; j < A.ps.n; ++j) {
+        double result = bitsd(kQuietNaN);
+        P.bad = bad_stream;  // a query's failure (never expected) flags its own percentile only
+        if (!base) {
+            const SelectArgs B = pct_args(A, j);
+            const Ranks R = ranks_for(B, n);
+            uint64_t k0 = 0, k1 = 0;
+            if (R.r1 != R.r0) {  // LINEAR: both adjacent ranks from one locate
+                P.rank_key_pair((uint64_t)R.r0, n, bmn, bmx, k0, k1);
+                k0 ^= P.flip;
+                k1 ^= P.flip;
+            } else {
+                k0 = P.rank_key((uint64_t)R.r0, n, bmn, bmx) ^ P.flip;
+            }
+            result = finish_value(B, R, k0, k1, beg, end, lane);
+        }
+        const uint32_t flags = base | (P.bad ? KRR_FLAG_CAPACITY | (P.bad << 8) : 0u);
+        if (lane == 0) {
+            A.out_v[(int64_t)j * A.S + s] = result;
+            A.out_f[(int64_t)j * A.S + s] = flags;
+        }
+    }
+    if (lane == 0) A.out_n[s] = (int64_t)n;
+    __syncthreads();
+}
+
+__device__ __forceinline__ void select_segment_multi(const MultiArgs& A, int64_t s, unsigned char* smem, int lane) {
+    const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    select_segment_multi_with(A, s, smem, lane, [&](SelectProc& P) {
+        // opaque bounds, as in select_segment: the retry loop must not hoist the address set-up
+        int64_t b = beg, e = end;
+        asm volatile("" : "+s"(b), "+s"(e));
+        return stream_segment<true>(A.vals, b, e, P, lane);
+    });
+}
+
+// refindex_gaps_segment for a set of percentiles: one NanCountProc stream, then one walk
+// from the nearer end per percentile (each re-reads at most half the segment).
+__device__ __forceinline__ void refindex_gaps_segment_multi(const MultiArgs& A, int64_t s, int lane) {
+    const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    NanCountProc C{0};
+    C.nn -= stream_segment<true>(A.vals, beg, end, C, lane);
+    const uint64_t n = (uint64_t)(end - beg) - C.nn;
+#pragma unroll 1
+    for (int j = 0; j < A.ps.n; ++j) {
+        double result = bitsd(kQuietNaN);
+        uint32_t flags = 0;
+        if (n == 0) {
+            flags = KRR_FLAG_EMPTY;
+        } else {
+            const uint64_t k = (uint64_t)rule_rank((int64_t)n, A.ps.p_num[j], A.ps.p_den[j], A.ps.ktab[j],
+                                                   A.ps.ktab_len[j]);
+            const bool back = k >= n / 2;
+            const uint64_t want = back ? n - 1 - k : k;  // present samples to skip
+            const int64_t step = back ? -1 : 1;
+            uint64_t run = 0;
+            uint64_t found = kQuietNaN;
+            bool done = false;
+            for (int64_t pos = back ? end - 1 : beg; !done && (back ? pos >= beg : pos < end);
+                 pos += step * kRefBlock * kWave) {
+                uint64_t u[kRefBlock];
+#pragma unroll
+                for (int b = 0; b < kRefBlock; ++b) {
+                    const int64_t i = pos + step * (b * kWave + lane);
+                    u[b] = (i >= beg && i < end) ? dbits(A.vals[i]) : kQuietNaN;
+                }
+                // (no unroll request: with the early exit the optimizer declines it, as in
+                // refindex_gaps_segment, and the forms it can unroll cost 26 more VGPRs)
+                for (int b = 0; b < kRefBlock; ++b) {
+                    if (done) break;
+                    const bool p = !is_nan_bits(u[b]);
+                    const uint64_t m = ballot(p);
+                    const uint32_t c = popc64(m);
+                    if (run + c > want) {
+                        const uint64_t sel = ballot(p && lane_prefix(m) == (uint32_t)(want - run));
+                        found = lane_bcast64(u[b], __ffsll((long long)sel) - 1);
+                        done = true;
+                    }
+                    run += c;
+                }
+            }
+            result = bitsd(found);
+        }
+        if (lane == 0) {
+            A.out_v[(int64_t)j * A.S + s] = result;
+            A.out_f[(int64_t)j * A.S + s] = flags;
+        }
+    }
+    if (lane == 0) A.out_n[s] = (int64_t)n;
+}
+
+// Compact CSR: P gathers per segment.
+__global__ __launch_bounds__(256) void k_refindex_dense_multi(MultiArgs A) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= A.S) return;
+    const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    const int64_t n = end - beg;
+    A.out_n[s] = n > 0 ? n : 0;
+    for (int j = 0; j < A.ps.n; ++j) {
+        double v = bitsd(kQuietNaN);
+        if (n > 0) v = A.vals[beg + rule_rank(n, A.ps.p_num[j], A.ps.p_den[j], A.ps.ktab[j], A.ps.ktab_len[j])];
+        A.out_v[(int64_t)j * A.S + s] = v;
+        A.out_f[(int64_t)j * A.S + s] = n > 0 ? 0u : KRR_FLAG_EMPTY;
+    }
+}
+
+// The fused launch for a set of percentiles: the S CPU segments (shared-buffer select, or
+// REF_INDEX on the gapped layout), then the M.S memory segments (none for
+// krr_segmented_percentiles), dispatched as in k_simple.
+template <int CPU_KIND>
+__global__ __launch_bounds__(64, KRR_SELECT_WAVES_PER_SIMD) void k_simple_multi(MultiArgs A, MaxArgs M) {
+    static_assert(CPU_KIND == CPU_SELECT || CPU_KIND == CPU_REF_GAPS, "the window kernels follow one rank");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int64_t total = A.S + M.S;
+    for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
+        if (b < A.S) {
+            const int64_t s = xcd_item(b, A.S, A.remap);
+            if constexpr (CPU_KIND == CPU_SELECT) select_segment_multi(A, s, smem, threadIdx.x);
+            else refindex_gaps_segment_multi(A, s, threadIdx.x);
+        } else {
+            max_segment<true>(M, xcd_item(b - A.S, M.S, M.remap), threadIdx.x);
+        }
+    }
+}
+
 // 32-byte result records for the multi-GPU gather (int64[4] per object):
 // cpu bits, mem bits, cpu count | cpu flags << 48, mem count | mem flags << 48.
 __global__ __launch_bounds__(256) void k_pack_records(int64_t S, const double* __restrict__ cv,
@@ -4561,6 +4781,201 @@ int krr_select_plan(int64_t max_segment_len, const krr_percentile_params* params
     out->probe = (!hsel && !sp.bottom && select_probe_pays(Lmax, sp.tkeep, need)) ? 1 : 0;
 #endif
     return KRR_OK;
+}
+
+}  // extern "C"
+
+// ---- Several percentiles from one pass ---------------------------------------
+namespace {
+
+int check_params_multi(krr_ctx* ctx, const krr_percentile_params* params, int32_t n_params) {
+    if (!params) return set_err(ctx, KRR_E_INVALID, "null params%s", "");
+    if (n_params < 1 || n_params > KRR_MAX_PERCENTILES)
+        return set_err(ctx, KRR_E_INVALID, "n_params must be in [1, KRR_MAX_PERCENTILES], got %s%lld", "",
+                       (long long)n_params);
+    for (int32_t j = 0; j < n_params; ++j) {
+        const int rc = check_params(ctx, &params[j]);
+        if (rc) return rc;
+        if (params[j].mode != params[0].mode)
+            return set_err(ctx, KRR_E_INVALID, "every percentile of a set takes the same mode (entry %s%lld differs)",
+                           "", (long long)j);
+    }
+    return KRR_OK;
+}
+
+PctSet pct_set(const krr_percentile_params* params, int32_t n_params) {
+    PctSet ps{};
+    ps.n = n_params;
+    ps.mode = params[0].mode;
+    for (int32_t j = 0; j < KRR_MAX_PERCENTILES; ++j) {
+        const krr_percentile_params& p = params[j < n_params ? j : 0];  // unused slots: a valid copy
+        ps.p_num[j] = p.p_num;
+        ps.p_den[j] = p.p_den;
+        ps.q[j] = p.q;
+        ps.ktab[j] = p.k_table;
+        ps.ktab_len[j] = p.k_table_len;
+    }
+    return ps;
+}
+
+// The launch rule: shared when the set's buffer at the longest segment fits the single pass.
+// (window_select's preference does not apply: the window kernels follow one rank.)
+void plan_multi(int64_t Lmax, const PctSet& ps, krr_multi_plan_info* out) {
+    *out = krr_multi_plan_info{};
+    if (ps.mode == KRR_PCT_REF_INDEX) {
+        out->shared = 1;
+        return;
+    }
+    const SidePlan sp = plan_side_multi(Lmax, ps);
+    const uint32_t need = capacity_for(sp.tkeep);
+    if (!single_pass_ok(need, sp.tkeep, Lmax, sp.bottom)) return;
+    out->shared = 1;
+    out->bottom = (int32_t)sp.bottom;
+    out->tkeep = sp.tkeep;
+    out->cap_keys = need;
+    out->lds_bytes = (int64_t)kSelectLdsFixed + (int64_t)need * 8;
+}
+
+// Lmax, the per-entry table check (check_table's), and the launch plan.
+int prepare_multi(krr_ctx* ctx, const krr_series* series, const krr_percentile_params* params, int32_t n_params,
+                  hipStream_t st, int64_t* Lmax, krr_multi_plan_info* plan) {
+    int rc = resolve_maxlen(ctx, series, st, Lmax);
+    if (rc) return rc;
+    for (int32_t j = 0; j < n_params; ++j)
+        if (params[j].k_table && params[j].mode != KRR_PCT_LINEAR && *Lmax >= params[j].k_table_len)
+            return set_err(ctx, KRR_E_INVALID, "k_table holds %s%lld entries, segments reach more slots", "",
+                           (long long)params[j].k_table_len);
+    plan_multi(*Lmax > 0 ? *Lmax : 1, pct_set(params, n_params), plan);
+    return KRR_OK;
+}
+
+MultiArgs multi_args(const krr_series* series, const krr_percentile_params* params, int32_t n_params, int64_t Lmax,
+                     const krr_multi_plan_info& plan, double* ov, int64_t* on, uint32_t* of) {
+    MultiArgs A{};
+    A.vals = series->values;
+    A.offs = series->offsets;
+    A.S = series->n_segments;
+    A.gaps = series->gaps_are_nan;
+    A.remap = Lmax < KRR_XCD_REMAP_MAXLEN ? 1 : 0;
+    A.cap = (uint32_t)plan.cap_keys;
+    A.ps = pct_set(params, n_params);
+    A.out_v = ov;
+    A.out_n = on;
+    A.out_f = of;
+    return A;
+}
+
+// The shared launch (plan.shared, not compact REF_INDEX): CPU segments, then M's memory segments.
+int launch_multi(krr_ctx* ctx, const MultiArgs& A, const MaxArgs& M, const krr_multi_plan_info& plan,
+                 hipStream_t st) {
+    const dim3 g(grid_for(A.S + M.S)), b(64);
+    if (A.ps.mode == KRR_PCT_REF_INDEX) {
+        hipLaunchKernelGGL((k_simple_multi<CPU_REF_GAPS>), g, b, 0, st, A, M);
+    } else {
+        size_t lds = (size_t)plan.lds_bytes;
+        if (lds < (size_t)KRR_LDS_MIN) lds = (size_t)KRR_LDS_MIN;
+        if (lds > ctx->max_lds) return set_err(ctx, KRR_E_CAPACITY, "select needs %s%lld B of LDS", "", (long long)lds);
+        (void)hipFuncSetAttribute((const void*)k_simple_multi<CPU_SELECT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)ctx->max_lds);
+        hipLaunchKernelGGL((k_simple_multi<CPU_SELECT>), g, b, lds, st, A, M);
+    }
+    KRR_HIP(ctx, hipGetLastError());
+    return KRR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int krr_multi_plan(int64_t max_segment_len, const krr_percentile_params* params, int32_t n_params,
+                   krr_multi_plan_info* out) {
+    if (!out || max_segment_len < 0) return KRR_E_INVALID;
+    const int rc = check_params_multi(nullptr, params, n_params);
+    if (rc) return rc;
+    plan_multi(max_segment_len > 0 ? max_segment_len : 1, pct_set(params, n_params), out);
+    return KRR_OK;
+}
+
+int krr_segmented_percentiles(krr_ctx* ctx, const krr_series* series, const krr_percentile_params* params,
+                              int32_t n_params, double* out_value, int64_t* out_count, uint32_t* out_flags,
+                              void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    int rc = check_series(ctx, series);
+    if (!rc) rc = check_params_multi(ctx, params, n_params);
+    if (rc) return rc;
+    if (n_params == 1) return krr_segmented_percentile(ctx, series, params, out_value, out_count, out_flags, stream);
+    const int64_t S = series->n_segments;
+    if (S == 0) return KRR_OK;
+    if (!out_value || !out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    hipStream_t st = (hipStream_t)stream;
+    int64_t Lmax = 0;
+    krr_multi_plan_info plan;
+    rc = prepare_multi(ctx, series, params, n_params, st, &Lmax, &plan);
+    if (rc) return rc;
+    if (!plan.shared) {  // the set does not share a buffer: the per-percentile paths, same layout
+        for (int32_t j = 0; j < n_params && !rc; ++j)
+            rc = krr_segmented_percentile(ctx, series, &params[j], out_value + (int64_t)j * S, out_count,
+                                          out_flags + (int64_t)j * S, stream);
+        return rc;
+    }
+    const MultiArgs A = multi_args(series, params, n_params, Lmax, plan, out_value, out_count, out_flags);
+    if (params[0].mode == KRR_PCT_REF_INDEX && !series->gaps_are_nan) {
+        hipLaunchKernelGGL(k_refindex_dense_multi, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, st, A);
+        KRR_HIP(ctx, hipGetLastError());
+        return KRR_OK;
+    }
+    MaxArgs M{nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr};
+    return launch_multi(ctx, A, M, plan, st);
+}
+
+int krr_simple_run_multi(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,
+                         const krr_percentile_params* params, int32_t n_params, double* cpu_value,
+                         int64_t* cpu_count, uint32_t* cpu_flags, double* mem_value, int64_t* mem_count,
+                         uint32_t* mem_flags, void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    if (!cpu || !mem) return set_err(ctx, KRR_E_INVALID, "null series%s", "");
+    if (cpu->n_segments != mem->n_segments)
+        return set_err(ctx, KRR_E_INVALID, "cpu and mem need one segment per object each%s", "");
+    int rc = check_series(ctx, cpu);
+    if (!rc) rc = check_series(ctx, mem);
+    if (!rc) rc = check_params_multi(ctx, params, n_params);
+    if (rc) return rc;
+    if (n_params == 1)
+        return krr_simple_run(ctx, cpu, mem, params, cpu_value, cpu_count, cpu_flags, mem_value, mem_count, mem_flags,
+                              stream);
+    const int64_t S = cpu->n_segments;
+    if (S == 0) return KRR_OK;
+    if (!cpu_value || !cpu_count || !cpu_flags || !mem_value || !mem_count || !mem_flags)
+        return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+    if (params[0].mode == KRR_PCT_REF_INDEX && !cpu->gaps_are_nan) {
+        // compact REF_INDEX is P gathers per segment: nothing to fuse with
+        rc = krr_segmented_percentiles(ctx, cpu, params, n_params, cpu_value, cpu_count, cpu_flags, stream);
+        if (!rc) rc = krr_segmented_max(ctx, mem, mem_value, mem_count, mem_flags, stream);
+        return rc;
+    }
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    hipStream_t st = (hipStream_t)stream;
+    int64_t Lmax = 0;
+    krr_multi_plan_info plan;
+    rc = prepare_multi(ctx, cpu, params, n_params, st, &Lmax, &plan);
+    if (rc) return rc;
+    if (!plan.shared) {
+        // one percentile rides the fused launch with the memory half, the others are
+        // percentile-only passes: P + 1 half-passes instead of 2 P
+        rc = krr_simple_run(ctx, cpu, mem, &params[0], cpu_value, cpu_count, cpu_flags, mem_value, mem_count,
+                            mem_flags, stream);
+        for (int32_t j = 1; j < n_params && !rc; ++j)
+            rc = krr_segmented_percentile(ctx, cpu, &params[j], cpu_value + (int64_t)j * S, cpu_count,
+                                          cpu_flags + (int64_t)j * S, stream);
+        return rc;
+    }
+    const MultiArgs A = multi_args(cpu, params, n_params, Lmax, plan, cpu_value, cpu_count, cpu_flags);
+    MaxArgs M{mem->values, mem->offsets, S, mem->gaps_are_nan, mem_value, mem_count, mem_flags};
+    M.remap = mem->max_segment_len > 0 && mem->max_segment_len >= KRR_XCD_REMAP_MAXLEN ? 0 : 1;
+    return launch_multi(ctx, A, M, plan, st);
 }
 
 }  // extern "C"

@@ -71,6 +71,58 @@ KRR_HD inline SidePlan plan_side(int64_t L, int32_t mode, int64_t p_num, int64_t
     return sp;
 }
 
+// Per-percentile scalars of a multi-percentile launch (krr_segmented_percentiles,
+// krr_simple_run_multi): fixed arrays, so the set travels as one kernel argument.
+struct PctSet {
+    int32_t n;     // percentiles in use, 1 .. KRR_MAX_PERCENTILES
+    int32_t mode;  // one krr_percentile_mode for the whole set
+    int64_t p_num[KRR_MAX_PERCENTILES], p_den[KRR_MAX_PERCENTILES];
+    double q[KRR_MAX_PERCENTILES];
+    const int64_t* ktab[KRR_MAX_PERCENTILES];  // krr_percentile_params.k_table (null: the exact floor)
+    int64_t ktab_len[KRR_MAX_PERCENTILES];
+};
+
+// plan_side for a set of percentiles sharing one candidate buffer: the rank queries only
+// read the buffer, so the top (bottom) keys kept for the innermost percentile hold every
+// percentile outside it.  Per percentile k, wide and the LINEAR float floor are plan_side's;
+// the buffer keeps max_j of the tops or max_j of the bottoms, whichever is smaller.  Both
+// maxima are non-decreasing in L (each term is), so a capacity sized for the launch's
+// longest segment covers every shorter one.
+KRR_HD inline SidePlan plan_side_multi(int64_t L, const PctSet& ps) {
+    SidePlan sp;
+    if (L <= 0) {
+        sp.tkeep = 1;
+        sp.bottom = 0;
+        return sp;
+    }
+    int64_t top = 0, bot = 0;
+    for (int j = 0; j < ps.n; ++j) {
+        int64_t k;
+        if (ps.mode == KRR_PCT_LINEAR) {
+            double v = (double)(L - 1) * ps.q[j];
+            k = (int64_t)floor(v);
+            if (k > L - 1) k = L - 1;
+            if (k < 0) k = 0;
+        } else {
+            k = exact_rank_hd(L, ps.p_num[j], ps.p_den[j]);
+        }
+        const int64_t wide = (ps.ktab[j] != nullptr && ps.mode != KRR_PCT_LINEAR) ? 2 : 0;
+        const int64_t t = L - k + 2 + wide, b = k + 4 + wide;
+        top = t > top ? t : top;
+        bot = b > bot ? b : bot;
+    }
+    if (top > L) top = L;
+    if (bot > L) bot = L;
+    if (top <= bot) {
+        sp.tkeep = (uint32_t)top;
+        sp.bottom = 0;
+    } else {
+        sp.tkeep = (uint32_t)bot;
+        sp.bottom = 1;
+    }
+    return sp;
+}
+
 // Fixed LDS of the select kernel ahead of the candidate keys: 256-bin
 // histogram (1 KiB) and the 64-key gather area (512 B).
 constexpr uint32_t kSelectLdsFixed = 1536;

@@ -1,3 +1,4 @@
 from .simple import SimpleStrategy
+from .simple_limit import SimpleLimitStrategy
 
-__all__ = ["SimpleStrategy"]
+__all__ = ["SimpleStrategy", "SimpleLimitStrategy"]
