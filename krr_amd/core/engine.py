@@ -60,6 +60,12 @@ class RawResults:
     mem_exact: Optional[dict] = None
 
 
+def _empty_results() -> RawResults:
+    """The results of a fleet without objects."""
+    e = np.zeros(0)
+    return RawResults(e, e.astype(np.int64), e.astype(np.uint32), e, e.astype(np.int64), e.astype(np.uint32))
+
+
 class SimpleEngine:
     def __init__(self, device: int = 0):
         self.device = int(device)
@@ -119,9 +125,7 @@ class SimpleEngine:
             raise ValueError("cpu and memory need one segment per object each")
         self.context()  # raises NativeUnavailable without the HIP library or a device
         if fleet.n_objects == 0:
-            e = np.zeros(0)
-            return RawResults(e, e.astype(np.int64), e.astype(np.uint32), e, e.astype(np.int64),
-                              e.astype(np.uint32))
+            return _empty_results()
         from krr_amd.core.distributed import unpack_records
 
         S = fleet.n_objects
@@ -135,7 +139,6 @@ class SimpleEngine:
         host = unpack_records(rec.numpy())
         return RawResults(host["cpu_value"], host["cpu_count"], host["cpu_flags"], host["mem_value"],
                           host["mem_count"], host["mem_flags"], loc)
-
 
     def run_packed_records(self, fleet: PackedFleet, params: _native.KrrPercentileParams):
         """The fused kernel pass over a (shard of a) fleet, returning its 32-B result
@@ -172,27 +175,32 @@ class SimpleEngine:
         exactness class >= 1 (``_locate_chunk``); returns its answers, else None."""
         import torch
 
-        from krr_amd.core.distributed import slice_fleet
-
         S = fleet.n_objects
-        bounds = self._chunk_bounds(fleet)
         ctx = self.context()
         dev = torch.device("cuda", self.device)
         out = {k: torch.empty(S, dtype=dt, device=dev) for k, dt in
                (("cpu_value", torch.float64), ("cpu_count", torch.int64), ("cpu_flags", torch.int32),
                 ("mem_value", torch.float64), ("mem_count", torch.int64), ("mem_flags", torch.int32))}
         loc = {r: tuple(np.full(S, -1, dtype=np.int64) for _ in range(3)) for r in ("cpu", "mem")} if locate else None
-        for lo, hi in bounds:
-            part = fleet if (lo, hi) == (0, S) else slice_fleet(fleet, lo, hi)
-            cv, co = self._to_device(part.cpu)
-            mv, mo = self._to_device(part.mem)
-            cs = ctx.series(cv, co, max(part.cpu.max_len, 1), part.cpu.gaps_are_nan)
-            ms = ctx.series(mv, mo, max(part.mem.max_len, 1), part.mem.gaps_are_nan)
+        for lo, hi, part, cs, ms in self._chunks(fleet):
             chunk_out = {k: v[lo:hi] for k, v in out.items()}
             ctx.simple_run(cs, ms, params, chunk_out, records=rec[lo:hi])
             if locate:
                 self._locate_chunk(ctx, part, cs, ms, params, chunk_out, loc, lo)
         return loc
+
+    def _chunks(self, fleet: PackedFleet):
+        """Per chunk of ``_chunk_bounds``: (lo, hi, the chunk's fleet, its CPU series, its memory
+        series), uploaded on the current stream when the generator reaches it."""
+        from krr_amd.core.distributed import slice_fleet
+
+        ctx = self.context()
+        for lo, hi in self._chunk_bounds(fleet):
+            part = fleet if (lo, hi) == (0, fleet.n_objects) else slice_fleet(fleet, lo, hi)
+            cv, co = self._to_device(part.cpu)
+            mv, mo = self._to_device(part.mem)
+            yield (lo, hi, part, ctx.series(cv, co, max(part.cpu.max_len, 1), part.cpu.gaps_are_nan),
+                   ctx.series(mv, mo, max(part.mem.max_len, 1), part.mem.gaps_are_nan))
 
     def _chunk_bounds(self, fleet: PackedFleet) -> list:
         """The object ranges a fleet runs as: whole when it is resident in HBM or within two
@@ -215,17 +223,13 @@ class SimpleEngine:
         class >= 1 are located per percentile (``_locate_chunk``)."""
         import torch
 
-        from krr_amd.core.distributed import slice_fleet
-
         params_list = list(params_list)
         if fleet.cpu.n_segments != fleet.mem.n_segments:
             raise ValueError("cpu and memory need one segment per object each")
         ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
         S, P = fleet.n_objects, len(params_list)
         if S == 0:
-            e = np.zeros(0)
-            return [RawResults(e, e.astype(np.int64), e.astype(np.uint32), e, e.astype(np.int64),
-                               e.astype(np.uint32)) for _ in range(P)]
+            return [_empty_results() for _ in range(P)]
         dev = torch.device("cuda", self.device)
         with torch.cuda.device(self.device):
             out = {k: torch.empty(shape, dtype=dt, device=dev) for k, dt, shape in
@@ -236,12 +240,7 @@ class SimpleEngine:
             for j, params in enumerate(params_list):
                 if needs_locate(fleet, params):
                     locs[j] = {r: tuple(np.full(S, -1, dtype=np.int64) for _ in range(3)) for r in ("cpu", "mem")}
-            for lo, hi in self._chunk_bounds(fleet):
-                part = fleet if (lo, hi) == (0, S) else slice_fleet(fleet, lo, hi)
-                cv, co = self._to_device(part.cpu)
-                mv, mo = self._to_device(part.mem)
-                cs = ctx.series(cv, co, max(part.cpu.max_len, 1), part.cpu.gaps_are_nan)
-                ms = ctx.series(mv, mo, max(part.mem.max_len, 1), part.mem.gaps_are_nan)
+            for lo, hi, part, cs, ms in self._chunks(fleet):
                 n = hi - lo
                 whole = n == S
                 # a chunk's rows are not contiguous in the [P, S] outputs: its own [P, n] block

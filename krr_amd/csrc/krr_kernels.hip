@@ -1042,103 +1042,122 @@ __device__ __forceinline__ void write_result(const SelectArgs& A, int64_t s, dou
 // either the single-pass candidate keys (cap x 8 B) or hselect's histogram
 // (kHistBins x 4 B) + collect buffer (kCollectCap x 8 B).
 
+// What select_stream leaves for the rank queries: present and NaN counts, the buffer's key range.
+struct Streamed {
+    uint64_t n, nnan, bmn, bmx;
+#ifdef KRR_DIAG
+    unsigned long long t_begin, t_final;  // before the probe, after the last stream
+#endif
+    // the flags the counts alone decide; a segment with any of them has no value
+    __device__ uint32_t flags(int32_t gaps) const { return !n ? KRR_FLAG_EMPTY : nnan && !gaps ? KRR_FLAG_NAN : 0u; }
+};
+
+// The single HBM pass of one CPU segment (SORTED_LOWER / LINEAR) by one wave, for one
+// percentile or a set: P set up on `smem` for the plan `sp`, the start-threshold probe, the
+// stream, and the buffer's key range.  `stream(P)` runs the segment's samples through P and
+// returns the NaN padding; `lowest_rank(n)` is the lowest rank of n present samples to be asked for.
+template <class Streamer, class LowestRank>
+__device__ __forceinline__ Streamed select_stream(SelectProc& P, const double* vals, int64_t beg, int64_t L,
+                                                  const SidePlan& sp, uint32_t cap, int32_t gaps,
+                                                  unsigned char* smem, int lane, Streamer stream,
+                                                  LowestRank lowest_rank) {
+    Streamed T;
+    P.buf = reinterpret_cast<uint64_t*>(smem + kSelectLdsFixed);
+    P.H = reinterpret_cast<uint32_t*>(smem);
+    P.small = reinterpret_cast<uint64_t*>(smem + 1024);
+    P.lane = lane;
+    P.cap = cap;
+    P.tkeep = sp.tkeep;
+    P.tstop = cap - kChunkElems / 2;
+    P.flip = sp.bottom ? ~0ull : 0ull;
+    P.cnt = 0;
+    P.bad = 0;
+#ifdef KRR_DIAG
+    for (int d = 0; d < D_WORDS; ++d) P.diag[d] = 0;
+    T.t_begin = __builtin_amdgcn_s_memtime();
+#endif
+    uint64_t thr0 = 0;  // inclusive at the lowest key: every sample is a candidate
+#if KRR_SELECT_PROBE
+    if (!sp.bottom && cap && select_probe_pays(L, sp.tkeep, cap)) thr0 = P.probe_threshold(vals, beg, L);
+#endif
+    uint32_t pad;
+    uint64_t nnan, n;
+#pragma unroll 1
+    for (;;) {
+        P.cnt = 0;
+        P.eqs = 0;
+        P.nnan_lane = 0;
+        P.bad = 0;
+        P.set_thr(thr0, 1u);
+        pad = stream(P);  // NaN padding slots
+        __syncthreads();
+        nnan = wave_sum_u32(P.nnan_lane) - pad;
+        n = gaps ? (uint64_t)L - nnan : (uint64_t)L;  // present samples
+        if (thr0 == 0 || n == 0 || (nnan && !gaps)) break;
+        // Speculative start: exact iff the lowest needed rank is held in buf (ranks below
+        // n - cnt - ties lie under thr0); else stream again from the lowest key.
+        const uint64_t ties = P.incl ? 0u : P.eqs;
+        if (!P.bad && (uint64_t)lowest_rank(n) >= n - P.cnt - ties) break;
+        thr0 = 0;
+    }
+#ifdef KRR_DIAG
+    T.t_final = __builtin_amdgcn_s_memtime();
+#endif
+    T.n = n;
+    T.nnan = nnan;
+    T.bmn = T.bmx = 0;
+    if (P.cnt) P.buf_minmax(T.bmn, T.bmx);
+    return T;
+}
+
+// One percentile's value from the streamed buffer: its ranks, the rank queries, finish_value.
+__device__ __forceinline__ double select_value(SelectProc& P, const SelectArgs& A, const Streamed& T, int64_t beg,
+                                               int64_t end, int lane) {
+    const Ranks R = ranks_for(A, T.n);
+    uint64_t k0 = 0, k1 = 0;
+#if KRR_PAIR_RANKS
+    if (R.r1 != R.r0) {  // LINEAR: both adjacent ranks from one locate
+        P.rank_key_pair((uint64_t)R.r0, T.n, T.bmn, T.bmx, k0, k1);
+        k0 ^= P.flip;
+        k1 ^= P.flip;
+    } else {
+        k0 = P.rank_key((uint64_t)R.r0, T.n, T.bmn, T.bmx) ^ P.flip;
+    }
+#else
+    // one rank-query body serves both ranks (a 1-2 iteration loop keeps it inlined once)
+    const int nq = R.r1 != R.r0 ? 2 : 1;
+#pragma unroll 1
+    for (int qi = 0; qi < nq; ++qi) {
+        const uint64_t kq = P.rank_key((uint64_t)(qi ? R.r1 : R.r0), T.n, T.bmn, T.bmx) ^ P.flip;
+        if (qi) k1 = kq;
+        else k0 = kq;
+    }
+#endif
+    return finish_value(A, R, k0, k1, beg, end, lane);
+}
+
 // One CPU segment (SORTED_LOWER / LINEAR) by one wave, single HBM pass.
-// `stream(P)` runs the segment's samples through P and returns the NaN padding.
 template <class Streamer>
 __device__ __forceinline__ void select_segment_with(const SelectArgs& A, int64_t s, unsigned char* smem, int lane,
                                                     Streamer stream) {
-    {
-        const int64_t beg = A.offs[s], end = A.offs[s + 1];
-        const int64_t L = end - beg;
-        const SidePlan sp = plan_side(L, A.mode, A.p_num, A.p_den, A.q, A.ktab != nullptr);
-        SelectProc P;
-        P.buf = reinterpret_cast<uint64_t*>(smem + kSelectLdsFixed);
-        P.H = reinterpret_cast<uint32_t*>(smem);
-        P.small = reinterpret_cast<uint64_t*>(smem + 1024);
-        P.lane = lane;
-        P.cap = A.cap;
-        P.tkeep = sp.tkeep;
-        P.tstop = A.cap - kChunkElems / 2;
-        P.flip = sp.bottom ? ~0ull : 0ull;
-        P.cnt = 0;
-        P.bad = 0;
+    const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    const int64_t L = end - beg;
+    const SidePlan sp = plan_side(L, A.mode, A.p_num, A.p_den, A.q, A.ktab != nullptr);
+    SelectProc P;
+    const Streamed T = select_stream(P, A.vals, beg, L, sp, A.cap, A.gaps, smem, lane, stream,
+                                     [&](uint64_t n) { return ranks_for(A, n).r0; });
+    uint32_t flags = T.flags(A.gaps);
+    const double result = flags ? bitsd(kQuietNaN) : select_value(P, A, T, beg, end, lane);
+    if (P.bad) flags |= KRR_FLAG_CAPACITY | (P.bad << 8);  // reason bits (diagnostic)
 #ifdef KRR_DIAG
-        for (int d = 0; d < D_WORDS; ++d) P.diag[d] = 0;
-        KRR_DIAG_T0(t_begin);
+    const unsigned long long t_end = __builtin_amdgcn_s_memtime();
+    P.diag[D_TOTAL] = t_end - T.t_begin;
+    P.diag[D_FINAL] = t_end - T.t_final;
+    if (lane == 0 && g_diag)
+        for (int d = 0; d < D_WORDS; ++d) g_diag[(size_t)s * D_WORDS + d] = P.diag[d];
 #endif
-        uint64_t thr0 = 0;  // inclusive at the lowest key: every sample is a candidate
-#if KRR_SELECT_PROBE
-        if (!sp.bottom && A.cap && select_probe_pays(L, sp.tkeep, A.cap)) thr0 = P.probe_threshold(A.vals, beg, L);
-#endif
-        uint32_t pad;
-        uint64_t nnan, n;
-#pragma unroll 1
-        for (;;) {
-            P.cnt = 0;
-            P.eqs = 0;
-            P.nnan_lane = 0;
-            P.bad = 0;
-            P.set_thr(thr0, 1u);
-            pad = stream(P);  // NaN padding slots
-            __syncthreads();
-            nnan = wave_sum_u32(P.nnan_lane) - pad;
-            n = A.gaps ? (uint64_t)L - nnan : (uint64_t)L;  // present samples
-            if (thr0 == 0 || n == 0 || (nnan && !A.gaps)) break;
-            // Speculative start: exact iff the lowest needed rank is held in buf
-            // (ranks below n - cnt - ties lie under thr0); else stream again from
-            // the lowest key.
-            const uint64_t ties = P.incl ? 0u : P.eqs;
-            if (!P.bad && (uint64_t)ranks_for(A, n).r0 >= n - P.cnt - ties) break;
-            thr0 = 0;
-        }
-#ifdef KRR_DIAG
-        KRR_DIAG_T0(t_final);
-#endif
-        uint64_t bmn = 0, bmx = 0;
-        if (P.cnt) P.buf_minmax(bmn, bmx);
-
-        uint32_t flags = 0;
-        double result = bitsd(kQuietNaN);
-        if (n == 0) {
-            flags |= KRR_FLAG_EMPTY;
-        } else if (nnan && !A.gaps) {
-            flags |= KRR_FLAG_NAN;
-        } else {
-            const Ranks R = ranks_for(A, n);
-            uint64_t k0 = 0, k1 = 0;
-#if KRR_PAIR_RANKS
-            if (R.r1 != R.r0) {  // LINEAR: both adjacent ranks from one locate
-                P.rank_key_pair((uint64_t)R.r0, n, bmn, bmx, k0, k1);
-                k0 ^= P.flip;
-                k1 ^= P.flip;
-            } else {
-                k0 = P.rank_key((uint64_t)R.r0, n, bmn, bmx) ^ P.flip;
-            }
-#else
-            // one rank-query body serves both ranks (a 1-2 iteration loop keeps it inlined once)
-            const int nq = R.r1 != R.r0 ? 2 : 1;
-#pragma unroll 1
-            for (int qi = 0; qi < nq; ++qi) {
-                const uint64_t kq = P.rank_key((uint64_t)(qi ? R.r1 : R.r0), n, bmn, bmx) ^ P.flip;
-                if (qi) k1 = kq;
-                else k0 = kq;
-            }
-#endif
-            result = finish_value(A, R, k0, k1, beg, end, lane);
-        }
-        if (P.bad) flags |= KRR_FLAG_CAPACITY | (P.bad << 8);  // reason bits (diagnostic)
-#ifdef KRR_DIAG
-        {
-            const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-            P.diag[D_TOTAL] = t_end - t_begin;
-            P.diag[D_FINAL] = t_end - t_final;
-            if (lane == 0 && g_diag)
-                for (int d = 0; d < D_WORDS; ++d) g_diag[(size_t)s * D_WORDS + d] = P.diag[d];
-        }
-#endif
-        write_result(A, s, result, n, flags, lane);
-        __syncthreads();
-    }
+    write_result(A, s, result, T.n, flags, lane);
+    __syncthreads();
 }
 
 __device__ __forceinline__ void select_segment(const SelectArgs& A, int64_t s, unsigned char* smem, int lane) {
@@ -2434,60 +2453,64 @@ struct RefArgs {
     int64_t* rec = nullptr;  // optional records, CPU half
 };
 
+// NaN-gapped layout: the k-th PRESENT sample (0-based, of n) of [beg, end) in position order,
+// by a walk from the nearer end in blocks of 16 x 64 slots whose loads are all in flight at
+// once (one HBM round trip per 1,024 slots, not per 64).  The inner loop asks to be unrolled;
+// with its early exit the optimizer declines (and says so), which is the form wanted: the
+// forms it can unroll cost 26 more VGPRs.
+__device__ __forceinline__ double refindex_walk(const double* vals, int64_t beg, int64_t end, uint64_t k, uint64_t n,
+                                                int lane) {
+    const bool back = k >= n / 2;
+    const uint64_t want = back ? n - 1 - k : k;  // present samples to skip
+    const int64_t step = back ? -1 : 1;
+    uint64_t run = 0;
+    uint64_t found = kQuietNaN;
+    bool done = false;
+    for (int64_t pos = back ? end - 1 : beg; !done && (back ? pos >= beg : pos < end);
+         pos += step * kRefBlock * kWave) {
+        uint64_t u[kRefBlock];
+#pragma unroll
+        for (int b = 0; b < kRefBlock; ++b) {
+            const int64_t i = pos + step * (b * kWave + lane);
+            u[b] = (i >= beg && i < end) ? dbits(vals[i]) : kQuietNaN;
+        }
+#pragma unroll
+        for (int b = 0; b < kRefBlock; ++b) {
+            if (done) break;
+            const bool p = !is_nan_bits(u[b]);
+            const uint64_t m = ballot(p);
+            const uint32_t c = popc64(m);
+            if (run + c > want) {
+                const uint64_t sel = ballot(p && lane_prefix(m) == (uint32_t)(want - run));
+                found = lane_bcast64(u[b], __ffsll((long long)sel) - 1);
+                done = true;
+            }
+            run += c;
+        }
+    }
+    return bitsd(found);
+}
+
 // NaN-gapped layout: the k-th PRESENT sample in position order.
 // ONE_SITE: the fused kernel's register budget (KRR_SELECT_WAVES_PER_SIMD) only fits
 // the one-site streaming loop; the standalone kernel uses the depth-2 loop.
 template <bool ONE_SITE>
 __device__ __forceinline__ void refindex_gaps_segment(const RefArgs& A, int64_t s, int lane) {
-    {
-        const int64_t beg = A.offs[s], end = A.offs[s + 1];
-        NanCountProc C{0};
-        C.nn -= stream_segment<ONE_SITE>(A.vals, beg, end, C, lane);
-        const uint64_t n = (uint64_t)(end - beg) - C.nn;
-        double result = bitsd(kQuietNaN);
-        uint32_t flags = 0;
-        if (n == 0) {
-            flags = KRR_FLAG_EMPTY;
-        } else {
-            const uint64_t k = (uint64_t)rule_rank((int64_t)n, A.p_num, A.p_den, A.ktab, A.ktab_len);
-            // walk from the nearer end in blocks of 16 x 64 slots whose loads are all
-            // in flight at once (one HBM round trip per 1,024 slots, not per 64)
-            const bool back = k >= n / 2;
-            const uint64_t want = back ? n - 1 - k : k;  // present samples to skip
-            const int64_t step = back ? -1 : 1;
-            uint64_t run = 0;
-            uint64_t found = kQuietNaN;
-            bool done = false;
-            for (int64_t pos = back ? end - 1 : beg; !done && (back ? pos >= beg : pos < end);
-                 pos += step * kRefBlock * kWave) {
-                uint64_t u[kRefBlock];
-#pragma unroll
-                for (int b = 0; b < kRefBlock; ++b) {
-                    const int64_t i = pos + step * (b * kWave + lane);
-                    u[b] = (i >= beg && i < end) ? dbits(A.vals[i]) : kQuietNaN;
-                }
-#pragma unroll
-                for (int b = 0; b < kRefBlock; ++b) {
-                    if (done) break;
-                    const bool p = !is_nan_bits(u[b]);
-                    const uint64_t m = ballot(p);
-                    const uint32_t c = popc64(m);
-                    if (run + c > want) {
-                        const uint64_t sel = ballot(p && lane_prefix(m) == (uint32_t)(want - run));
-                        found = lane_bcast64(u[b], __ffsll((long long)sel) - 1);
-                        done = true;
-                    }
-                    run += c;
-                }
-            }
-            result = bitsd(found);
-        }
-        if (lane == 0) {
-            A.out_v[s] = result;
-            A.out_n[s] = (int64_t)n;
-            A.out_f[s] = flags;
-            put_record(A.rec, s, 0, result, n, flags);
-        }
+    const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    NanCountProc C{0};
+    C.nn -= stream_segment<ONE_SITE>(A.vals, beg, end, C, lane);
+    const uint64_t n = (uint64_t)(end - beg) - C.nn;
+    const uint32_t flags = n ? 0u : KRR_FLAG_EMPTY;
+    double result = bitsd(kQuietNaN);
+    if (n) {
+        const uint64_t k = (uint64_t)rule_rank((int64_t)n, A.p_num, A.p_den, A.ktab, A.ktab_len);
+        result = refindex_walk(A.vals, beg, end, k, n, lane);
+    }
+    if (lane == 0) {
+        A.out_v[s] = result;
+        A.out_n[s] = (int64_t)n;
+        A.out_f[s] = flags;
+        put_record(A.rec, s, 0, result, n, flags);
     }
 }
 
@@ -2674,22 +2697,13 @@ struct MultiArgs {
 
 // The one-percentile arguments ranks_for / finish_value read, for percentile j of the set.
 __device__ __forceinline__ SelectArgs pct_args(const MultiArgs& A, int j) {
-    SelectArgs B{};
-    B.vals = A.vals;
-    B.offs = A.offs;
-    B.S = A.S;
-    B.mode = A.ps.mode;
-    B.gaps = A.gaps;
-    B.p_num = A.ps.p_num[j];
-    B.p_den = A.ps.p_den[j];
-    B.q = A.ps.q[j];
-    B.ktab = A.ps.ktab[j];
-    B.ktab_len = A.ps.ktab_len[j];
-    return B;
+    return SelectArgs{A.vals, A.offs, A.S, A.ps.mode, A.gaps, A.ps.p_num[j], A.ps.p_den[j], A.ps.q[j], A.ps.ktab[j],
+                      A.ps.ktab_len[j]};  // the fields after ktab_len: their defaults
 }
 
-// select_segment_with for a set of percentiles: one SelectProc sized by the set's plan,
-// one stream, then the rank queries and finish_value once per percentile.
+// select_segment_with for a set of percentiles: one SelectProc sized by the set's plan, one
+// select_stream that holds the LOWEST rank any percentile needs, then select_value once per
+// percentile.
 template <class Streamer>
 __device__ __forceinline__ void select_segment_multi_with(const MultiArgs& A, int64_t s, unsigned char* smem,
                                                           int lane, Streamer stream) {
@@ -2697,78 +2711,28 @@ __device__ __forceinline__ void select_segment_multi_with(const MultiArgs& A, in
     const int64_t L = end - beg;
     const SidePlan sp = plan_side_multi(L, A.ps);
     SelectProc P;
-    P.buf = reinterpret_cast<uint64_t*>(smem + kSelectLdsFixed);
-    P.H = reinterpret_cast<uint32_t*>(smem);
-    P.small = reinterpret_cast<uint64_t*>(smem + 1024);
-    P.lane = lane;
-    P.cap = A.cap;
-    P.tkeep = sp.tkeep;
-    P.tstop = A.cap - kChunkElems / 2;
-    P.flip = sp.bottom ? ~0ull : 0ull;
-    P.cnt = 0;
-    P.bad = 0;
-#ifdef KRR_DIAG
-    for (int d = 0; d < D_WORDS; ++d) P.diag[d] = 0;
-#endif
-    uint64_t thr0 = 0;  // inclusive at the lowest key: every sample is a candidate
-#if KRR_SELECT_PROBE
-    if (!sp.bottom && A.cap && select_probe_pays(L, sp.tkeep, A.cap)) thr0 = P.probe_threshold(A.vals, beg, L);
-#endif
-    uint32_t pad;
-    uint64_t nnan, n;
-#pragma unroll 1
-    for (;;) {
-        P.cnt = 0;
-        P.eqs = 0;
-        P.nnan_lane = 0;
-        P.bad = 0;
-        P.set_thr(thr0, 1u);
-        pad = stream(P);  // NaN padding slots
-        __syncthreads();
-        nnan = wave_sum_u32(P.nnan_lane) - pad;
-        n = A.gaps ? (uint64_t)L - nnan : (uint64_t)L;  // present samples
-        if (thr0 == 0 || n == 0 || (nnan && !A.gaps)) break;
-        // Speculative start: exact iff the LOWEST rank any percentile needs is held in buf
-        // (ranks below n - cnt - ties lie under thr0); else stream again from the lowest key.
-        const uint64_t ties = P.incl ? 0u : P.eqs;
+    const Streamed T = select_stream(P, A.vals, beg, L, sp, A.cap, A.gaps, smem, lane, stream, [&](uint64_t n) {
         int64_t rmin = (int64_t)n;
 #pragma unroll 1
         for (int j = 0; j < A.ps.n; ++j) {
             const int64_t r = ranks_for(pct_args(A, j), n).r0;
             rmin = r < rmin ? r : rmin;
         }
-        if (!P.bad && (uint64_t)rmin >= n - P.cnt - ties) break;
-        thr0 = 0;
-    }
-    uint64_t bmn = 0, bmx = 0;
-    if (P.cnt) P.buf_minmax(bmn, bmx);
-
-    const uint32_t base = n == 0 ? KRR_FLAG_EMPTY : (nnan && !A.gaps) ? KRR_FLAG_NAN : 0u;
+        return rmin;
+    });
+    const uint32_t base = T.flags(A.gaps);
     const uint32_t bad_stream = P.bad;
 #pragma unroll 1
     for (int j = 0; j < A.ps.n; ++j) {
-        double result = bitsd(kQuietNaN);
         P.bad = bad_stream;  // a query's failure (never expected) flags its own percentile only
-        if (!base) {
-            const SelectArgs B = pct_args(A, j);
-            const Ranks R = ranks_for(B, n);
-            uint64_t k0 = 0, k1 = 0;
-            if (R.r1 != R.r0) {  // LINEAR: both adjacent ranks from one locate
-                P.rank_key_pair((uint64_t)R.r0, n, bmn, bmx, k0, k1);
-                k0 ^= P.flip;
-                k1 ^= P.flip;
-            } else {
-                k0 = P.rank_key((uint64_t)R.r0, n, bmn, bmx) ^ P.flip;
-            }
-            result = finish_value(B, R, k0, k1, beg, end, lane);
-        }
+        const double result = base ? bitsd(kQuietNaN) : select_value(P, pct_args(A, j), T, beg, end, lane);
         const uint32_t flags = base | (P.bad ? KRR_FLAG_CAPACITY | (P.bad << 8) : 0u);
         if (lane == 0) {
             A.out_v[(int64_t)j * A.S + s] = result;
             A.out_f[(int64_t)j * A.S + s] = flags;
         }
     }
-    if (lane == 0) A.out_n[s] = (int64_t)n;
+    if (lane == 0) A.out_n[s] = (int64_t)T.n;
     __syncthreads();
 }
 
@@ -2792,46 +2756,14 @@ __device__ __forceinline__ void refindex_gaps_segment_multi(const MultiArgs& A, 
 #pragma unroll 1
     for (int j = 0; j < A.ps.n; ++j) {
         double result = bitsd(kQuietNaN);
-        uint32_t flags = 0;
-        if (n == 0) {
-            flags = KRR_FLAG_EMPTY;
-        } else {
+        if (n) {
             const uint64_t k = (uint64_t)rule_rank((int64_t)n, A.ps.p_num[j], A.ps.p_den[j], A.ps.ktab[j],
                                                    A.ps.ktab_len[j]);
-            const bool back = k >= n / 2;
-            const uint64_t want = back ? n - 1 - k : k;  // present samples to skip
-            const int64_t step = back ? -1 : 1;
-            uint64_t run = 0;
-            uint64_t found = kQuietNaN;
-            bool done = false;
-            for (int64_t pos = back ? end - 1 : beg; !done && (back ? pos >= beg : pos < end);
-                 pos += step * kRefBlock * kWave) {
-                uint64_t u[kRefBlock];
-#pragma unroll
-                for (int b = 0; b < kRefBlock; ++b) {
-                    const int64_t i = pos + step * (b * kWave + lane);
-                    u[b] = (i >= beg && i < end) ? dbits(A.vals[i]) : kQuietNaN;
-                }
-                // (no unroll request: with the early exit the optimizer declines it, as in
-                // refindex_gaps_segment, and the forms it can unroll cost 26 more VGPRs)
-                for (int b = 0; b < kRefBlock; ++b) {
-                    if (done) break;
-                    const bool p = !is_nan_bits(u[b]);
-                    const uint64_t m = ballot(p);
-                    const uint32_t c = popc64(m);
-                    if (run + c > want) {
-                        const uint64_t sel = ballot(p && lane_prefix(m) == (uint32_t)(want - run));
-                        found = lane_bcast64(u[b], __ffsll((long long)sel) - 1);
-                        done = true;
-                    }
-                    run += c;
-                }
-            }
-            result = bitsd(found);
+            result = refindex_walk(A.vals, beg, end, k, n, lane);
         }
         if (lane == 0) {
             A.out_v[(int64_t)j * A.S + s] = result;
-            A.out_f[(int64_t)j * A.S + s] = flags;
+            A.out_f[(int64_t)j * A.S + s] = n ? 0u : KRR_FLAG_EMPTY;
         }
     }
     if (lane == 0) A.out_n[s] = (int64_t)n;
@@ -3614,16 +3546,33 @@ int resolve_maxlen(krr_ctx* ctx, const krr_series* s, hipStream_t st, int64_t* o
     return KRR_OK;
 }
 
-// A launch reading krr_percentile_params.k_table: every segment's count must index it.
-int check_table(krr_ctx* ctx, const krr_series* s, const krr_percentile_params* p, hipStream_t st) {
-    if (!p->k_table || p->mode == KRR_PCT_LINEAR) return KRR_OK;
-    int64_t Lmax = 0;
-    int rc = resolve_maxlen(ctx, s, st, &Lmax);
-    if (rc) return rc;
-    if (Lmax >= p->k_table_len)
+// A launch reading krr_percentile_params.k_table: every segment's count (at most Lmax) must index it.
+int check_table_len(krr_ctx* ctx, const krr_percentile_params* p, int64_t Lmax) {
+    if (p->k_table && p->mode != KRR_PCT_LINEAR && Lmax >= p->k_table_len)
         return set_err(ctx, KRR_E_INVALID, "k_table holds %s%lld entries, segments reach more slots", "",
                        (long long)p->k_table_len);
     return KRR_OK;
+}
+
+int check_table(krr_ctx* ctx, const krr_series* s, const krr_percentile_params* p, hipStream_t st) {
+    if (!p->k_table || p->mode == KRR_PCT_LINEAR) return KRR_OK;
+    int64_t Lmax = 0;
+    const int rc = resolve_maxlen(ctx, s, st, &Lmax);
+    return rc ? rc : check_table_len(ctx, p, Lmax);
+}
+
+// The KRR_LDS_MIN floor and the device's ceiling for a select launch's dynamic LDS.
+int clamp_lds(krr_ctx* ctx, size_t* lds) {
+    if (*lds < (size_t)KRR_LDS_MIN) *lds = (size_t)KRR_LDS_MIN;
+    if (*lds > ctx->max_lds) return set_err(ctx, KRR_E_CAPACITY, "select needs %s%lld B of LDS", "", (long long)*lds);
+    return KRR_OK;
+}
+
+// The memory half of a launch (k_max, or the fused kernels' second half).
+MaxArgs max_args(const krr_series* mem, double* value, int64_t* count, uint32_t* flags, int64_t* records) {
+    MaxArgs M{mem->values, mem->offsets, mem->n_segments, mem->gaps_are_nan, value, count, flags, records};
+    M.remap = mem->max_segment_len > 0 && mem->max_segment_len >= KRR_XCD_REMAP_MAXLEN ? 0 : 1;
+    return M;
 }
 
 int check_series(krr_ctx* ctx, const krr_series* s) {
@@ -3641,10 +3590,8 @@ int plan_select(krr_ctx* ctx, const krr_series* series, const krr_percentile_par
                 hipStream_t st, double* ov, int64_t* on, uint32_t* of, SelectArgs* A, size_t* lds, bool fused) {
     int64_t Lmax = 0;
     int rc = resolve_maxlen(ctx, series, st, &Lmax);
+    if (!rc) rc = check_table_len(ctx, params, Lmax);
     if (rc) return rc;
-    if (params->k_table && params->mode != KRR_PCT_LINEAR && Lmax >= params->k_table_len)
-        return set_err(ctx, KRR_E_INVALID, "k_table holds %s%lld entries, segments reach more slots", "",
-                       (long long)params->k_table_len);
     const SidePlan sp = plan_side(Lmax, params->mode, params->p_num, params->p_den, params->q,
                                   params->k_table != nullptr);
     const uint32_t need = capacity_for(sp.tkeep);
@@ -3678,8 +3625,8 @@ int plan_select(krr_ctx* ctx, const krr_series* series, const krr_percentile_par
         }
     }
     *lds = kSelectLdsFixed + (hsel ? (KRR_WSEL ? window_lds(A->wcap) : kHselectLds) : (size_t)cap * 8);
-    if (*lds < (size_t)KRR_LDS_MIN) *lds = (size_t)KRR_LDS_MIN;
-    if (*lds > ctx->max_lds) return set_err(ctx, KRR_E_CAPACITY, "select needs %s%lld B of LDS", "", (long long)*lds);
+    rc = clamp_lds(ctx, lds);
+    if (rc) return rc;
     if (hsel && KRR_WSEL && A->wcap != kWselCapLong) {
         // launch k counts its misses into counter (k & 1) and zeroes counter ((k + 1) & 1),
         // which launch k - 1's miss pass has read by then (stream order, or the event below);
@@ -3775,7 +3722,7 @@ int krr_create(int device, krr_ctx** out_ctx) {
                           (const void*)k_select<SEL_WINDOW_LONG>, (const void*)k_simple<CPU_SELECT>,
                           (const void*)k_simple<CPU_HSELECT>, (const void*)k_simple<CPU_HSELECT_LONG>,
                           (const void*)k_simple<CPU_SELECT, true>, (const void*)k_simple<CPU_HSELECT, true>,
-                          (const void*)k_simple<CPU_HSELECT_LONG, true>})
+                          (const void*)k_simple<CPU_HSELECT_LONG, true>, (const void*)k_simple_multi<CPU_SELECT>})
         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->max_lds);
     (void)hipFuncSetAttribute((const void*)k_sketch_build, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)c->max_lds);
@@ -3852,8 +3799,7 @@ int krr_segmented_max(krr_ctx* ctx, const krr_series* series, double* out_value,
     if (!out_value || !out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
     DeviceGuard g(ctx->device);
     if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-    MaxArgs A{series->values, series->offsets, S, series->gaps_are_nan, out_value, out_count, out_flags};
-    A.remap = series->max_segment_len > 0 && series->max_segment_len >= KRR_XCD_REMAP_MAXLEN ? 0 : 1;
+    const MaxArgs A = max_args(series, out_value, out_count, out_flags, nullptr);
     hipLaunchKernelGGL(k_max, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
     KRR_HIP(ctx, hipGetLastError());
     return KRR_OK;
@@ -3916,8 +3862,7 @@ int krr_simple_run_forward(krr_ctx* ctx, const krr_series* cpu, const krr_series
     DeviceGuard g(ctx->device);
     if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
     hipStream_t st = (hipStream_t)stream;
-    MaxArgs M{mem->values, mem->offsets, S, mem->gaps_are_nan, mem_value, mem_count, mem_flags, records};
-    M.remap = mem->max_segment_len > 0 && mem->max_segment_len >= KRR_XCD_REMAP_MAXLEN ? 0 : 1;
+    MaxArgs M = max_args(mem, mem_value, mem_count, mem_flags, records);
     if (fwd_units > 0) {
         M.fwd_src = (const double2*)forward_src;
         M.fwd_dst = (double2*)forward_dst;
@@ -4836,15 +4781,13 @@ void plan_multi(int64_t Lmax, const PctSet& ps, krr_multi_plan_info* out) {
     out->lds_bytes = (int64_t)kSelectLdsFixed + (int64_t)need * 8;
 }
 
-// Lmax, the per-entry table check (check_table's), and the launch plan.
+// Lmax, the per-entry table check, and the launch plan.
 int prepare_multi(krr_ctx* ctx, const krr_series* series, const krr_percentile_params* params, int32_t n_params,
                   hipStream_t st, int64_t* Lmax, krr_multi_plan_info* plan) {
     int rc = resolve_maxlen(ctx, series, st, Lmax);
     if (rc) return rc;
-    for (int32_t j = 0; j < n_params; ++j)
-        if (params[j].k_table && params[j].mode != KRR_PCT_LINEAR && *Lmax >= params[j].k_table_len)
-            return set_err(ctx, KRR_E_INVALID, "k_table holds %s%lld entries, segments reach more slots", "",
-                           (long long)params[j].k_table_len);
+    for (int32_t j = 0; j < n_params && !rc; ++j) rc = check_table_len(ctx, &params[j], *Lmax);
+    if (rc) return rc;
     plan_multi(*Lmax > 0 ? *Lmax : 1, pct_set(params, n_params), plan);
     return KRR_OK;
 }
@@ -4873,10 +4816,8 @@ int launch_multi(krr_ctx* ctx, const MultiArgs& A, const MaxArgs& M, const krr_m
         hipLaunchKernelGGL((k_simple_multi<CPU_REF_GAPS>), g, b, 0, st, A, M);
     } else {
         size_t lds = (size_t)plan.lds_bytes;
-        if (lds < (size_t)KRR_LDS_MIN) lds = (size_t)KRR_LDS_MIN;
-        if (lds > ctx->max_lds) return set_err(ctx, KRR_E_CAPACITY, "select needs %s%lld B of LDS", "", (long long)lds);
-        (void)hipFuncSetAttribute((const void*)k_simple_multi<CPU_SELECT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)ctx->max_lds);
+        const int rc = clamp_lds(ctx, &lds);
+        if (rc) return rc;
         hipLaunchKernelGGL((k_simple_multi<CPU_SELECT>), g, b, lds, st, A, M);
     }
     KRR_HIP(ctx, hipGetLastError());
@@ -4973,9 +4914,7 @@ int krr_simple_run_multi(krr_ctx* ctx, const krr_series* cpu, const krr_series* 
         return rc;
     }
     const MultiArgs A = multi_args(cpu, params, n_params, Lmax, plan, cpu_value, cpu_count, cpu_flags);
-    MaxArgs M{mem->values, mem->offsets, S, mem->gaps_are_nan, mem_value, mem_count, mem_flags};
-    M.remap = mem->max_segment_len > 0 && mem->max_segment_len >= KRR_XCD_REMAP_MAXLEN ? 0 : 1;
-    return launch_multi(ctx, A, M, plan, st);
+    return launch_multi(ctx, A, max_args(mem, mem_value, mem_count, mem_flags, nullptr), plan, st);
 }
 
 }  // extern "C"

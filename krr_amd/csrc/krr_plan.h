@@ -39,14 +39,10 @@ struct SidePlan {
     uint32_t bottom;  // 1: keep the smallest keys (flip the order)
 };
 
-KRR_HD inline SidePlan plan_side(int64_t L, int32_t mode, int64_t p_num, int64_t p_den, double q,
-                                 bool table = false) {
-    SidePlan sp;
-    if (L <= 0) {
-        sp.tkeep = 1;
-        sp.bottom = 0;
-        return sp;
-    }
+// One percentile's terms at L >= 1 slots: the keys its top side (`top`) and its bottom side
+// (`bot`) must keep, margins included, before the clamp to L.
+KRR_HD inline void side_terms(int64_t L, int32_t mode, int64_t p_num, int64_t p_den, double q, bool table,
+                              int64_t& top, int64_t& bot) {
     int64_t k;
     if (mode == KRR_PCT_LINEAR) {
         double v = (double)(L - 1) * q;
@@ -57,18 +53,30 @@ KRR_HD inline SidePlan plan_side(int64_t L, int32_t mode, int64_t p_num, int64_t
         k = exact_rank_hd(L, p_num, p_den);
     }
     const int64_t wide = (table && mode != KRR_PCT_LINEAR) ? 2 : 0;
-    int64_t top = L - k + 2 + wide;
-    int64_t bot = k + 4 + wide;
+    top = L - k + 2 + wide;
+    bot = k + 4 + wide;
+}
+
+// The cheaper side of a segment of L slots, at most L keys (L <= 0: one key, top side).
+KRR_HD inline SidePlan side_of(int64_t L, int64_t top, int64_t bot) {
+    SidePlan sp;
+    if (L <= 0) {
+        sp.tkeep = 1;
+        sp.bottom = 0;
+        return sp;
+    }
     if (top > L) top = L;
     if (bot > L) bot = L;
-    if (top <= bot) {
-        sp.tkeep = (uint32_t)top;
-        sp.bottom = 0;
-    } else {
-        sp.tkeep = (uint32_t)bot;
-        sp.bottom = 1;
-    }
+    sp.bottom = top <= bot ? 0 : 1;
+    sp.tkeep = (uint32_t)(sp.bottom ? bot : top);
     return sp;
+}
+
+KRR_HD inline SidePlan plan_side(int64_t L, int32_t mode, int64_t p_num, int64_t p_den, double q,
+                                 bool table = false) {
+    int64_t top = 0, bot = 0;
+    if (L > 0) side_terms(L, mode, p_num, p_den, q, table, top, bot);
+    return side_of(L, top, bot);
 }
 
 // Per-percentile scalars of a multi-percentile launch (krr_segmented_percentiles,
@@ -84,43 +92,18 @@ struct PctSet {
 
 // plan_side for a set of percentiles sharing one candidate buffer: the rank queries only
 // read the buffer, so the top (bottom) keys kept for the innermost percentile hold every
-// percentile outside it.  Per percentile k, wide and the LINEAR float floor are plan_side's;
-// the buffer keeps max_j of the tops or max_j of the bottoms, whichever is smaller.  Both
-// maxima are non-decreasing in L (each term is), so a capacity sized for the launch's
-// longest segment covers every shorter one.
+// percentile outside it.  The buffer keeps max_j of the tops or max_j of the bottoms
+// (side_terms per percentile), whichever is smaller.  Both maxima are non-decreasing in L
+// (each term is), so a capacity sized for the launch's longest segment covers every shorter one.
 KRR_HD inline SidePlan plan_side_multi(int64_t L, const PctSet& ps) {
-    SidePlan sp;
-    if (L <= 0) {
-        sp.tkeep = 1;
-        sp.bottom = 0;
-        return sp;
-    }
     int64_t top = 0, bot = 0;
-    for (int j = 0; j < ps.n; ++j) {
-        int64_t k;
-        if (ps.mode == KRR_PCT_LINEAR) {
-            double v = (double)(L - 1) * ps.q[j];
-            k = (int64_t)floor(v);
-            if (k > L - 1) k = L - 1;
-            if (k < 0) k = 0;
-        } else {
-            k = exact_rank_hd(L, ps.p_num[j], ps.p_den[j]);
-        }
-        const int64_t wide = (ps.ktab[j] != nullptr && ps.mode != KRR_PCT_LINEAR) ? 2 : 0;
-        const int64_t t = L - k + 2 + wide, b = k + 4 + wide;
+    for (int j = 0; L > 0 && j < ps.n; ++j) {
+        int64_t t, b;
+        side_terms(L, ps.mode, ps.p_num[j], ps.p_den[j], ps.q[j], ps.ktab[j] != nullptr, t, b);
         top = t > top ? t : top;
         bot = b > bot ? b : bot;
     }
-    if (top > L) top = L;
-    if (bot > L) bot = L;
-    if (top <= bot) {
-        sp.tkeep = (uint32_t)top;
-        sp.bottom = 0;
-    } else {
-        sp.tkeep = (uint32_t)bot;
-        sp.bottom = 1;
-    }
-    return sp;
+    return side_of(L, top, bot);
 }
 
 // Fixed LDS of the select kernel ahead of the candidate keys: 256-bin
@@ -195,7 +178,7 @@ KRR_HD inline bool select_probe_pays(int64_t L, uint32_t tkeep, uint32_t cap) {
 }
 
 // `bottom`: the plan keeps the smallest keys.  The start-threshold probe only
-// runs for the top side (krr_kernels.hip select_segment_with), so the probe-backed
+// runs for the top side (krr_kernels.hip select_stream), so the probe-backed
 // capacity is top-side only; a low percentile of a long series (p5 of 50,400
 // slots keeps ~2,500 keys) would otherwise stream from the lowest key into a big
 // buffer and compact a dozen times per segment.

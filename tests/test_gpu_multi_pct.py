@@ -213,6 +213,53 @@ def test_single_percentile_equals_simple_run(gpu, mode, gaps):
     assert np.array_equal(outs[0][0][0].view(np.uint64), one["cpu_value"].cpu().numpy().view(np.uint64))
 
 
+@pytest.mark.parametrize("gaps", [False, True])
+@pytest.mark.parametrize("mode", MODES)
+def test_set_rows_equal_single_percentile_bits(gpu, mode, gaps):
+    """The set's rows against krr_segmented_percentile per percentile, bit for bit: both paths
+    take their value from the same rank query and finish, so even a LINEAR zero keeps its sign."""
+    import torch
+
+    from krr_amd import _native
+
+    ctx, dev = gpu
+    rng = np.random.default_rng(41)
+    x, offs, _ = ragged(rng, 2048, 2047, gaps)
+    S = 48  # the eight fixed lengths and 40 random ones
+    offs = offs[:S + 1].copy()
+    x = x[:offs[-1]].copy()
+    # zeros of both signs: the lowest ranks of segment 5, the highest of (negated) segment 7
+    x[offs[7]:offs[8]] *= -1.0
+    for s, at, run in ((5, 200, 300), (7, 900, 400)):
+        x[offs[s] + at:offs[s] + at + run] = np.where(rng.random(run) < 0.5, 0.0, -0.0)
+    Lmax = int(np.diff(offs).max())
+    assert Lmax == 2047
+    cs = ctx.series(torch.from_numpy(x).to(dev), torch.from_numpy(offs).to(dev), Lmax, gaps)
+    zero_rows = 0
+    for ps in ((95, 99), (1, 5)):
+        plist = params_of(ps, mode)
+        assert _native.multi_plan(Lmax, plist).shared == 1, (mode, gaps, ps)
+        v = torch.full((2, S), -1.0, dtype=torch.float64, device=dev)
+        n = torch.full((S,), -1, dtype=torch.int64, device=dev)
+        f = torch.full((2, S), -1, dtype=torch.int32, device=dev)
+        ctx.segmented_percentiles(cs, plist, v, n, f)
+        for j, prm in enumerate(plist):
+            v1 = torch.full((S,), -2.0, dtype=torch.float64, device=dev)
+            n1 = torch.full((S,), -2, dtype=torch.int64, device=dev)
+            f1 = torch.full((S,), -2, dtype=torch.int32, device=dev)
+            ctx.segmented_percentile(cs, prm, v1, n1, f1)
+            torch.cuda.synchronize()
+            a, b = v[j].cpu().numpy(), v1.cpu().numpy()
+            same = (a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))
+            bad = np.flatnonzero(~same)
+            assert bad.size == 0, (mode, gaps, ps, j, bad[:5], a[bad[:5]], b[bad[:5]])
+            assert np.array_equal(n.cpu().numpy(), n1.cpu().numpy()), (mode, gaps, ps, j)
+            assert np.array_equal(f[j].cpu().numpy(), f1.cpu().numpy()), (mode, gaps, ps, j)
+            zero_rows += int((b[[5, 7]] == 0).sum())
+    if mode != "ref_index":  # (REF_INDEX goes by position, not by rank among the values)
+        assert zero_rows >= 4  # the zero runs are where the ranks fall, in both segments
+
+
 def test_argument_errors(gpu):
     import torch
 
