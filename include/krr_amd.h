@@ -276,6 +276,49 @@ int krr_simple_run_multi(krr_ctx* ctx, const krr_series* cpu, const krr_series* 
                          int64_t* cpu_count /* [S] */, uint32_t* cpu_flags /* [P*S] */, double* mem_value,
                          int64_t* mem_count, uint32_t* mem_flags, void* stream);
 
+/* ---- CPU as the max over pods of each pod's percentile (cpu_aggregation = "pods_max") ----
+ * The flat rule above takes one percentile over an object's concatenated pods (KRR 1.0.0);
+ * later KRR takes a percentile per pod (quantile_over_time) and the max over the pods, so
+ * that one hot pod is not diluted among idle siblings.
+ *
+ * krr_group_max folds per-item results into per-group results: group g owns the items
+ * [group_offsets[g], group_offsets[g + 1]) (device int64[n_groups + 1]); row j of the inputs
+ * is in_value / in_flags[j * n_items + i] (1 <= n_rows <= KRR_MAX_PERCENTILES rows, e.g. the
+ * percentiles of krr_segmented_percentiles), in_count[n_items] is shared.  Per group and row,
+ * over its items in order:
+ *   - items flagged KRR_FLAG_EMPTY are skipped; out_count = the sum of the others' counts;
+ *   - no item left: value = quiet NaN, flags = KRR_FLAG_EMPTY, out_arg = -1;
+ *   - else flags = the OR of the contributing items' flags (bits 8..15 included);
+ *   - a contributing item with KRR_FLAG_NAN or KRR_FLAG_CAPACITY, or with a NaN value (LINEAR
+ *     over +Inf and -Inf): value = quiet NaN, out_arg = the first such item (np.max's rule);
+ *   - else value = the FIRST maximal item under float comparison, its own bits (-0.0 == +0.0:
+ *     the earlier one wins; Python max()'s rule, as krr_segmented_max), out_arg = its index
+ *     within the group.
+ * Outputs: out_value / out_flags / out_arg[j * n_groups + g], out_count[n_groups]; out_arg may
+ * be NULL.  records (may be NULL; n_rows must be 1): only the CPU half of each group's 32-byte
+ * record is written (words 0 and 2); the memory half stays untouched.  n_groups == 0 writes
+ * nothing.  One wave per group; no atomics. */
+int krr_group_max(krr_ctx* ctx, int64_t n_groups, const int64_t* group_offsets, int32_t n_rows, int64_t n_items,
+                  const double* in_value, const int64_t* in_count, const uint32_t* in_flags, double* out_value,
+                  int64_t* out_count, uint32_t* out_flags, int64_t* out_arg, int64_t* records, void* stream);
+
+/* krr_simple_run_records with the CPU rule above: cpu_pods holds ONE SEGMENT PER POD (a pod's
+ * samples in timestamp order; in the dense layout its slots), pod_groups (device
+ * int64[n_objects + 1], pod_groups[0] == 0, pod_groups[n_objects] == cpu_pods->n_segments) the
+ * pods of each object, mem one segment per object (n_objects = mem->n_segments).  One fused
+ * launch streams every value once — the pod segments as its CPU items, planned by the pod
+ * series' max_segment_len, then the memory segments — and krr_group_max follows on the stream.
+ * pod_value / pod_count / pod_flags [n_pods] (caller-owned, kept as outputs) equal
+ * krr_segmented_percentile over cpu_pods; cpu_value / cpu_count / cpu_flags / cpu_pod
+ * [n_objects] their fold (cpu_pod may be NULL); the memory outputs and records as
+ * krr_simple_run_records.  Synchronises the stream once (the pod_groups check).
+ * KRR_E_INVALID: a null pointer, pod_groups not spanning the pod segments. */
+int krr_simple_run_pods(krr_ctx* ctx, const krr_series* cpu_pods, const int64_t* pod_groups, const krr_series* mem,
+                        const krr_percentile_params* params, double* pod_value, int64_t* pod_count,
+                        uint32_t* pod_flags, double* cpu_value, int64_t* cpu_count, uint32_t* cpu_flags,
+                        int64_t* cpu_pod, double* mem_value, int64_t* mem_count, uint32_t* mem_flags,
+                        int64_t* records, void* stream);
+
 /* Counters of the ctx since krr_create (synchronises the device): segments whose
  * one-pass window select (wselect) missed and were finished by the two-pass
  * histogram select.  Diagnostic: results are exact either way. */

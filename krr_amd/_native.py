@@ -89,6 +89,8 @@ EXPORTED_SYMBOLS = (
     "krr_multi_plan",
     "krr_segmented_percentiles",
     "krr_simple_run_multi",
+    "krr_group_max",
+    "krr_simple_run_pods",
     "krr_get_stats",
     "krr_comm_unique_id",
     "krr_comm_init",
@@ -311,6 +313,10 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_segmented_percentiles.restype = ctypes.c_int
         lib.krr_simple_run_multi.argtypes = [vp, sp, sp, pp, i32, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_multi.restype = ctypes.c_int
+        lib.krr_group_max.argtypes = [vp, i64, vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_group_max.restype = ctypes.c_int
+        lib.krr_simple_run_pods.argtypes = [vp, sp, vp, sp, pp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_simple_run_pods.restype = ctypes.c_int
         lib.krr_get_stats.argtypes = [vp, ctypes.POINTER(i64)]
         lib.krr_get_stats.restype = ctypes.c_int
         lib.krr_comm_unique_id.argtypes = [vp, vp]
@@ -538,6 +544,62 @@ class Context:
             out["cpu_value"].data_ptr(), out["cpu_count"].data_ptr(), out["cpu_flags"].data_ptr(),
             out["mem_value"].data_ptr(), out["mem_count"].data_ptr(), out["mem_flags"].data_ptr(),
             self._stream(stream)))
+
+    def group_max(self, group_offsets, in_value, in_count, in_flags, out_value, out_count, out_flags,
+                  out_arg=None, records=None, stream=None) -> None:
+        """Per group the first maximal item with np.max's NaN propagation (krr_group_max).
+        group_offsets: int64 [G + 1] device tensor into the items; in_value float64 and in_flags
+        int32 [n_rows, n_items] (or [n_items]), in_count int64 [n_items]; out_value / out_flags /
+        out_arg [n_rows, G], out_count int64 [G].  records (int64 [G, 4], device or page-locked
+        host; one row only): the CPU half of each record (words 0 and 2) is written."""
+        _check_tensor(group_offsets, "int64")
+        G = group_offsets.numel() - 1
+        n_items = in_count.numel()
+        rows = int(in_value.shape[0]) if in_value.dim() == 2 else 1
+        _check_tensor(in_value, "float64", rows * n_items)
+        _check_tensor(in_count, "int64", n_items)
+        _check_tensor(in_flags, "int32", rows * n_items)
+        _check_tensor(out_value, "float64", rows * G)
+        _check_tensor(out_count, "int64", G)
+        _check_tensor(out_flags, "int32", rows * G)
+        if out_arg is not None:
+            _check_tensor(out_arg, "int64", rows * G)
+        if records is not None:
+            _check_tensor(records, "int64", 4 * G, host_pinned_ok=True)
+        self._check(self._lib.krr_group_max(
+            self._h, G, group_offsets.data_ptr(), rows, n_items, in_value.data_ptr(), in_count.data_ptr(),
+            in_flags.data_ptr(), out_value.data_ptr(), out_count.data_ptr(), out_flags.data_ptr(),
+            out_arg.data_ptr() if out_arg is not None else None,
+            records.data_ptr() if records is not None else None, self._stream(stream)))
+
+    def simple_run_pods(self, cpu_pods: KrrSeries, pod_groups, mem: KrrSeries, params: KrrPercentileParams,
+                        out: dict, stream=None, records=None) -> None:
+        """simple_run with CPU = the max over an object's pods of each pod's percentile
+        (krr_simple_run_pods).  cpu_pods: one segment per pod; pod_groups: int64 [S + 1] device
+        tensor, the pods of each object; mem: one segment per object.  out: simple_run's six
+        tensors [S] plus pod_value / pod_count / pod_flags [n_pods] (each pod's own result) and,
+        optionally, cpu_pod int64 [S] (the winning pod's index within its object, -1: none).
+        Synchronises the stream once (the pod_groups check)."""
+        S, n_pods = mem.n_segments, cpu_pods.n_segments
+        _check_tensor(pod_groups, "int64", S + 1)
+        for k, dt in (("cpu_value", "float64"), ("cpu_count", "int64"), ("cpu_flags", "int32"),
+                      ("mem_value", "float64"), ("mem_count", "int64"), ("mem_flags", "int32")):
+            _check_tensor(out[k], dt, S)
+        for k, dt in (("pod_value", "float64"), ("pod_count", "int64"), ("pod_flags", "int32")):
+            _check_tensor(out[k], dt, n_pods)
+        cpu_pod = out.get("cpu_pod")
+        if cpu_pod is not None:
+            _check_tensor(cpu_pod, "int64", S)
+        if records is not None:
+            _check_tensor(records, "int64", 4 * S, host_pinned_ok=True)
+        params = self._bound(params, cpu_pods)
+        self._check(self._lib.krr_simple_run_pods(
+            self._h, ctypes.byref(cpu_pods), pod_groups.data_ptr(), ctypes.byref(mem), ctypes.byref(params),
+            out["pod_value"].data_ptr(), out["pod_count"].data_ptr(), out["pod_flags"].data_ptr(),
+            out["cpu_value"].data_ptr(), out["cpu_count"].data_ptr(), out["cpu_flags"].data_ptr(),
+            cpu_pod.data_ptr() if cpu_pod is not None else None,
+            out["mem_value"].data_ptr(), out["mem_count"].data_ptr(), out["mem_flags"].data_ptr(),
+            records.data_ptr() if records is not None else None, self._stream(stream)))
 
     def pack_records(self, out: dict, records, stream=None) -> None:
         """out: the six result tensors; records: int64 [S, 4] device tensor."""

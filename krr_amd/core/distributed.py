@@ -176,9 +176,15 @@ def slice_series(ps, lo: int, hi: int):
     if exact is not None:
         exact = exact[lo:hi]
     sources = getattr(ps, "sources", None)
-    return PackedSeries(ps.values[a:b], offs, int(lens.max()) if lens.size else 0, ps.gaps_are_nan,
-                        exact if exact is not None and exact.any() else None,
-                        sources[lo:hi] if exact is not None and exact.any() else None)
+    out = PackedSeries(ps.values[a:b], offs, int(lens.max()) if lens.size else 0, ps.gaps_are_nan,
+                       exact if exact is not None and exact.any() else None,
+                       sources[lo:hi] if exact is not None and exact.any() else None)
+    groups = getattr(ps, "pod_groups", None)
+    if groups is not None:  # the pod boundaries of these objects, both rebased
+        ga, gb = int(groups[lo]), int(groups[hi])
+        out.pod_groups = (groups[lo:hi + 1] - ga).astype(np.int64)
+        out.pod_offsets = (ps.pod_offsets[ga:gb + 1] - a).astype(np.int64)
+    return out
 
 
 def slice_fleet(fleet, lo: int, hi: int):

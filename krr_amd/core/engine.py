@@ -58,6 +58,10 @@ class RawResults:
     locate: Optional[dict] = None
     cpu_exact: Optional[dict] = None
     mem_exact: Optional[dict] = None
+    # cpu_aggregation = "pods_max", on request: each pod segment's own result (pod_value,
+    # pod_count, pod_flags [n_pods]), the winning pod's index within its object (cpu_pod [S],
+    # -1: none) and, for HistoryData, krr_locate's answers over the pod segments ("locate")
+    pods: Optional[dict] = None
 
 
 def _empty_results() -> RawResults:
@@ -118,7 +122,12 @@ class SimpleEngine:
         ctx.simple_run(cs, ms, params, out, stream=stream)
         return out
 
-    def run_packed(self, fleet: PackedFleet, params: _native.KrrPercentileParams) -> RawResults:
+    def run_packed(self, fleet: PackedFleet, params: _native.KrrPercentileParams, aggregation: str = "concat",
+                   return_pods: bool = False) -> RawResults:
+        """``aggregation``: "concat" (one percentile over an object's concatenated pods) or
+        "pods_max" (the max over its pods of each pod's percentile, krr_simple_run_pods; the
+        CPU series needs pod boundaries).  ``return_pods`` (pods_max): also the pod-level
+        results (RawResults.pods)."""
         import torch
 
         if fleet.cpu.n_segments != fleet.mem.n_segments:
@@ -134,16 +143,24 @@ class SimpleEngine:
             # the launch writes the 32-B records straight into page-locked host memory
             # (krr_simple_run_records with a mapped host buffer): one sync, no D2H copies
             rec = torch.empty((S, 4), dtype=torch.int64, pin_memory=True)
-            loc = self._run_chunks(fleet, params, rec, locate=locate)
+            pods = {} if return_pods and aggregation == "pods_max" else None
+            loc = self._run_chunks(fleet, params, rec, locate=locate, aggregation=aggregation, pods=pods)
             torch.cuda.current_stream(self.device).synchronize()
         host = unpack_records(rec.numpy())
+        if pods is not None:
+            pod_loc = pods.pop("locate", None)
+            pods = {k: torch.cat(v).cpu().numpy() for k, v in pods.items()}  # S > 0: at least one chunk
+            pods["pod_flags"] = pods["pod_flags"].view(np.uint32)
+            pods["locate"] = pod_loc
         return RawResults(host["cpu_value"], host["cpu_count"], host["cpu_flags"], host["mem_value"],
-                          host["mem_count"], host["mem_flags"], loc)
+                          host["mem_count"], host["mem_flags"], loc, pods=pods)
 
-    def run_packed_records(self, fleet: PackedFleet, params: _native.KrrPercentileParams):
+    def run_packed_records(self, fleet: PackedFleet, params: _native.KrrPercentileParams,
+                           aggregation: str = "concat"):
         """The fused kernel pass over a (shard of a) fleet, returning its 32-B result
-        records as an int64 [S, 4] device tensor (krr_simple_run_records: written by the
-        same launch) on the current stream — what a rank sends to rank 0."""
+        records as an int64 [S, 4] device tensor (krr_simple_run_records, or
+        krr_simple_run_pods for ``aggregation`` "pods_max": written by the same launches) on
+        the current stream — what a rank sends to rank 0."""
         import torch
 
         if fleet.cpu.n_segments != fleet.mem.n_segments:
@@ -155,7 +172,7 @@ class SimpleEngine:
         if S == 0:
             return rec
         with torch.cuda.device(self.device):
-            self._run_chunks(fleet, params, rec)
+            self._run_chunks(fleet, params, rec, aggregation=aggregation)
             # the host buffers may be pinned and released by the caller: finish the copies
             torch.cuda.current_stream(self.device).synchronize()
         return rec
@@ -167,14 +184,22 @@ class SimpleEngine:
     chunk_bytes = 16 << 30
 
     def _run_chunks(self, fleet: PackedFleet, params: _native.KrrPercentileParams, rec,
-                    locate: bool = False) -> Optional[dict]:
+                    locate: bool = False, aggregation: str = "concat", pods: Optional[dict] = None) -> Optional[dict]:
         """Upload + fused launch per chunk of objects, records rows into ``rec`` (device or
         page-locked host), all on the current stream: a chunk's device buffers are released
         to the caching allocator after its launch is enqueued, which reuses them in stream
         order for the next chunk.  ``locate``: also krr_locate over each chunk's segments of
-        exactness class >= 1 (``_locate_chunk``); returns its answers, else None."""
+        exactness class >= 1 (``_locate_chunk``); returns its answers, else None.
+        ``aggregation`` "pods_max": krr_simple_run_pods per chunk over its pod segments;
+        ``pods`` (a dict) then collects the chunks' pod-level device tensors and, with
+        ``locate``, krr_locate's answers over the pod segments (the CPU side of the exact path
+        is resolved per pod, krr_amd.core.exact.resolve_pods)."""
         import torch
 
+        if aggregation not in ("concat", "pods_max"):
+            raise ValueError(f"unknown cpu aggregation {aggregation!r}; expected 'concat' or 'pods_max'")
+        if aggregation == "pods_max":
+            return self._run_chunks_pods(fleet, params, rec, locate, pods)
         S = fleet.n_objects
         ctx = self.context()
         dev = torch.device("cuda", self.device)
@@ -187,6 +212,51 @@ class SimpleEngine:
             ctx.simple_run(cs, ms, params, chunk_out, records=rec[lo:hi])
             if locate:
                 self._locate_chunk(ctx, part, cs, ms, params, chunk_out, loc, lo)
+        return loc
+
+    def _run_chunks_pods(self, fleet: PackedFleet, params, rec, locate: bool, pods: Optional[dict]) -> Optional[dict]:
+        import torch
+
+        from krr_amd.core.packing import PackedSeries, pod_view
+
+        if fleet.cpu.pod_offsets is None or fleet.cpu.pod_groups is None:
+            pod_view(fleet.cpu)  # raises the ValueError that names the packer
+        S, n_pods = fleet.n_objects, fleet.cpu.n_pods
+        ctx = self.context()
+        dev = torch.device("cuda", self.device)
+        out = {k: torch.empty(S, dtype=dt, device=dev) for k, dt in
+               (("cpu_value", torch.float64), ("cpu_count", torch.int64), ("cpu_flags", torch.int32),
+                ("cpu_pod", torch.int64), ("mem_value", torch.float64), ("mem_count", torch.int64),
+                ("mem_flags", torch.int32))}
+        loc = {r: tuple(np.full(S, -1, dtype=np.int64) for _ in range(3)) for r in ("cpu", "mem")} if locate else None
+        pod_loc = None
+        if locate and fleet.cpu.exact is not None and params.mode == _native.KRR_PCT_SORTED_LOWER:
+            pod_loc = {"cpu": tuple(np.full(n_pods, -1, dtype=np.int64) for _ in range(3))}
+        if pods is not None:
+            pods.update({"pod_value": [], "pod_count": [], "pod_flags": [], "cpu_pod": [], "locate": pod_loc})
+        pod_lo = 0
+        for lo, hi, part, cs, ms in self._chunks(fleet):
+            view = pod_view(part.cpu)
+            po = torch.from_numpy(np.ascontiguousarray(view.offsets)).to(dev)
+            pg = torch.from_numpy(np.ascontiguousarray(part.cpu.pod_groups, dtype=np.int64)).to(dev)
+            pcs = ctx.series(cs._keep[0], po, max(view.max_len, 1), view.gaps_are_nan)
+            n = view.n_segments
+            chunk_out = {k: v[lo:hi] for k, v in out.items()}
+            chunk_out.update(pod_value=torch.empty(n, dtype=torch.float64, device=dev),
+                             pod_count=torch.empty(n, dtype=torch.int64, device=dev),
+                             pod_flags=torch.empty(n, dtype=torch.int32, device=dev))
+            ctx.simple_run_pods(pcs, pg, ms, params, chunk_out, records=rec[lo:hi])
+            if pods is not None:
+                for k in ("pod_value", "pod_count", "pod_flags", "cpu_pod"):
+                    pods[k].append(chunk_out[k])
+            if locate:
+                self._locate_chunk(ctx, part, cs, ms, params, chunk_out, loc, lo, names=("mem",))
+                if pod_loc is not None and view.exact is not None:
+                    pod_out = {"cpu_value": chunk_out["pod_value"], "cpu_count": chunk_out["pod_count"],
+                               "cpu_flags": chunk_out["pod_flags"]}
+                    self._locate_chunk(ctx, PackedFleet(view, PackedSeries(part.mem.values, part.mem.offsets, 0)),
+                                       pcs, ms, params, pod_out, pod_loc, pod_lo, names=("cpu",))
+            pod_lo += n
         return loc
 
     def _chunks(self, fleet: PackedFleet):
@@ -260,7 +330,8 @@ class SimpleEngine:
                            host["mem_value"], host["mem_count"], host["mem_flags"].view(np.uint32), locs[j])
                 for j in range(P)]
 
-    def _locate_chunk(self, ctx, part: PackedFleet, cs, ms, params, out: dict, loc: dict, lo: int) -> None:
+    def _locate_chunk(self, ctx, part: PackedFleet, cs, ms, params, out: dict, loc: dict, lo: int,
+                      names=("cpu", "mem")) -> None:
         """krr_locate for the chunk's class >= 1 segments that select one sample: memory
         (rank -1: the first maximal element, simple.py:29) and SORTED_LOWER CPU (rank k of
         the stable sort).  REF_INDEX needs no search (its position IS k) and LINEAR is defined
@@ -270,7 +341,7 @@ class SimpleEngine:
         torch.cuda.current_stream(self.device).synchronize()
         dev = torch.device("cuda", self.device)
         for name, ps, series in (("cpu", part.cpu, cs), ("mem", part.mem, ms)):
-            if ps.exact is None:
+            if ps.exact is None or name not in names:
                 continue
             rank = locate_ranks(name, ps.exact, out[f"{name}_count"].cpu().numpy(),
                                 out[f"{name}_flags"].cpu().numpy(), params)

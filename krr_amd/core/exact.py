@@ -89,4 +89,43 @@ def resolve(fleet: PackedFleet, raw, params) -> None:
         setattr(raw, f"{name}_exact", out)
 
 
-__all__ = ["resolve", "sample_at"]
+def resolve_pods(fleet: PackedFleet, raw, params) -> None:
+    """``resolve`` for cpu_aggregation = "pods_max" (``raw`` from SimpleEngine.run_packed with
+    ``return_pods``).  Memory is resolved as ever.  CPU: every pod of an object of class >= 1
+    is resolved at pod granularity (the rules above over the pod segments, krr_locate's
+    answers in ``raw.pods["locate"]``), and the object's answer is Python ``max()`` over its
+    pods' own Decimals — the host decides, because class 2 pods can tie as floats and differ
+    as Decimals; ``max()`` keeps the first maximal pod, as the kernel's fold does.  Objects
+    with a pod whose answer is NaN by the NaN rules, or a NaN sample as a pod's answer, get no
+    entry: the strategy's rules apply to the folded flags and count."""
+    import dataclasses
+
+    from krr_amd.core.engine import RawResults
+    from krr_amd.core.packing import pod_view
+
+    plain_cpu = dataclasses.replace(fleet.cpu, exact=None, sources=None)
+    resolve(PackedFleet(plain_cpu, fleet.mem), raw, params)
+    if fleet.cpu.exact is None or params.mode == _native.KRR_PCT_LINEAR:
+        return
+    pods = raw.pods
+    view = pod_view(fleet.cpu)
+    none = np.zeros(0)
+    pod_raw = RawResults(pods["pod_value"], pods["pod_count"], pods["pod_flags"], none, none.astype(np.int64),
+                         none.astype(np.uint32), pods.get("locate"))
+    resolve(PackedFleet(view, dataclasses.replace(fleet.mem, exact=None, sources=None)), pod_raw, params)
+    per_pod = pod_raw.cpu_exact or {}
+    groups = np.asarray(fleet.cpu.pod_groups)
+    out: dict = {}
+    for s in np.flatnonzero(fleet.cpu.exact).tolist():
+        js = [j for j in range(int(groups[s]), int(groups[s + 1]))
+              if not int(pods["pod_flags"][j]) & _native.KRR_FLAG_EMPTY]
+        if not js or any(j not in per_pod for j in js):
+            continue
+        ds = [per_pod[j] for j in js]
+        if any(getattr(d, "is_nan", lambda: d != d)() for d in ds):
+            continue
+        out[s] = max(ds)
+    raw.cpu_exact = out
+
+
+__all__ = ["resolve", "resolve_pods", "sample_at"]

@@ -39,6 +39,16 @@ class PackedSeries:
     # class >= 1 segments the tuple of its pod sample lists, which positions index into
     exact: Optional[np.ndarray] = None
     sources: Optional[list] = None
+    # The pod boundaries inside the segments (CPU series; cpu_aggregation = "pods_max"): pod
+    # segment j is values[pod_offsets[j]:pod_offsets[j + 1]] (int64 [n_pods + 1]) and object
+    # s owns the pod segments pod_groups[s] .. pod_groups[s + 1] (int64 [S + 1]), so that
+    # pod_offsets[pod_groups[s]] == offsets[s].  None: the packer kept no pod boundaries.
+    pod_offsets: Optional[np.ndarray] = None
+    pod_groups: Optional[np.ndarray] = None
+
+    @property
+    def n_pods(self) -> int:
+        return 0 if self.pod_offsets is None else len(self.pod_offsets) - 1
 
     @property
     def n_segments(self) -> int:
@@ -58,12 +68,54 @@ class PackedFleet:
         return self.cpu.n_segments
 
 
-def _from_chunks(chunks: list[np.ndarray], lens: list[int], gaps: bool = False) -> PackedSeries:
+def pod_fields(pod_lens, pods_per_object) -> tuple[np.ndarray, np.ndarray]:
+    """(pod_offsets, pod_groups) of a PackedSeries from its kept pods' lengths (fleet order)
+    and the number of kept pods per object."""
+    pod_offsets = np.zeros(len(pod_lens) + 1, dtype=np.int64)
+    if len(pod_lens):
+        np.cumsum(np.asarray(pod_lens, dtype=np.int64), out=pod_offsets[1:])
+    pod_groups = np.zeros(len(pods_per_object) + 1, dtype=np.int64)
+    if len(pods_per_object):
+        np.cumsum(np.asarray(pods_per_object, dtype=np.int64), out=pod_groups[1:])
+    return pod_offsets, pod_groups
+
+
+def pod_view(ps: PackedSeries) -> PackedSeries:
+    """The same values as ONE SEGMENT PER POD (cpu_aggregation = "pods_max"): offsets are the
+    pod offsets; a pod takes its object's exactness class (an upper bound of its own) and its
+    own sample list as ``sources``.  Raises ValueError for a series packed without pod
+    boundaries (the device packer, krr_amd.core.device_pack, keeps none)."""
+    if ps.pod_offsets is None or ps.pod_groups is None:
+        raise ValueError("cpu_aggregation='pods_max' needs the pod boundaries (PackedSeries.pod_offsets / "
+                         "pod_groups), which this series was packed without: the device packer "
+                         "(krr_amd.core.device_pack.DevicePacker) keeps none; pack on the host (pack_histories, "
+                         "pack_prometheus, pack_dense_grid, pack_query_range_bodies)")
+    pod_offsets = np.asarray(ps.pod_offsets, dtype=np.int64)
+    per_object = np.diff(np.asarray(ps.pod_groups, dtype=np.int64))
+    exact = sources = None
+    if ps.exact is not None:
+        exact = np.repeat(np.asarray(ps.exact), per_object)
+        sources = []
+        for s, k in enumerate(per_object.tolist()):
+            pods = ps.sources[s]
+            sources.extend([None] * k if pods is None else [(samples,) for samples in pods])
+        if len(sources) != exact.size:
+            raise ValueError("pod boundaries and pod sample lists disagree")
+    lens = np.diff(pod_offsets)
+    return PackedSeries(ps.values, pod_offsets, int(lens.max(initial=0)), ps.gaps_are_nan, exact, sources)
+
+
+def _from_chunks(chunks: list[np.ndarray], lens: list[int], gaps: bool = False,
+                 pods_per_object: Optional[list[int]] = None) -> PackedSeries:
+    """``pods_per_object``: every chunk is one pod; the kept pods per object."""
     offsets = np.zeros(len(lens) + 1, dtype=np.int64)
     if lens:
         np.cumsum(np.asarray(lens, dtype=np.int64), out=offsets[1:])
     values = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.float64)
-    return PackedSeries(values.astype(np.float64, copy=False), offsets, int(max(lens, default=0)), gaps)
+    ps = PackedSeries(values.astype(np.float64, copy=False), offsets, int(max(lens, default=0)), gaps)
+    if pods_per_object is not None:
+        ps.pod_offsets, ps.pod_groups = pod_fields([c.size for c in chunks], pods_per_object)
+    return ps
 
 
 # Exactness class of a HistoryData segment — what its samples' float64 images stand for
@@ -160,8 +212,14 @@ def pack_resource(histories: Sequence[Mapping], resource: ResourceType) -> Packe
     offsets = np.zeros(lens.size + 1, dtype=np.int64)
     np.cumsum(lens, out=offsets[1:])
     exact = cls if cls.any() else None
-    return PackedSeries(values, offsets, int(lens.max(initial=0)), False, exact,
-                        sources if exact is not None else None)
+    ps = PackedSeries(values, offsets, int(lens.max(initial=0)), False, exact,
+                      sources if exact is not None else None)
+    if resource == ResourceType.CPU:
+        # the pod boundaries, from the histories themselves (O(pods), whichever path packed)
+        per_object = [[len(x) for x in (h.get(resource) or {}).values() if len(x)] for h in histories]
+        ps.pod_offsets, ps.pod_groups = pod_fields([n for lens_o in per_object for n in lens_o],
+                                                   [len(lens_o) for lens_o in per_object])
+    return ps
 
 
 def pack_histories(histories: Sequence[Mapping]) -> PackedFleet:
@@ -182,15 +240,18 @@ def pack_prometheus(per_object_pod_results: Iterable[Sequence]) -> PackedSeries:
     (K8sObjectData.pods order), for ONE resource."""
     chunks: list[np.ndarray] = []
     lens: list[int] = []
+    kept: list[int] = []
     for pod_results in per_object_pod_results:
-        n = 0
+        n = k = 0
         for pr in pod_results:
             v = _pod_values(pr)
             if v is not None and v.size:
                 chunks.append(v)
                 n += v.size
+                k += 1
         lens.append(n)
-    return _from_chunks(chunks, lens)
+        kept.append(k)
+    return _from_chunks(chunks, lens, pods_per_object=kept)
 
 
 def pack_dense_grid(per_object_pods: Sequence[Sequence[tuple[np.ndarray, np.ndarray]]], start: float,
@@ -199,7 +260,8 @@ def pack_dense_grid(per_object_pods: Sequence[Sequence[tuple[np.ndarray, np.ndar
     start + i*step; a pod sample lands in its slot, every other slot is NaN
     (absent).  per_object_pods[o] = [(timestamps, values) per pod].  Because each
     pod keeps its slots in time order and pods stay in order, the present samples
-    of a segment are exactly the compact layout's samples, in the same order."""
+    of a segment are exactly the compact layout's samples, in the same order.  Every pod is
+    a pod segment of ``slots`` slots (``pod_offsets``), with or without present samples."""
     chunks: list[np.ndarray] = []
     lens: list[int] = []
     for pods in per_object_pods:
@@ -214,4 +276,4 @@ def pack_dense_grid(per_object_pods: Sequence[Sequence[tuple[np.ndarray, np.ndar
             chunks.append(grid)
             n += slots
         lens.append(n)
-    return _from_chunks(chunks, lens, gaps=True)
+    return _from_chunks(chunks, lens, gaps=True, pods_per_object=[len(pods) for pods in per_object_pods])

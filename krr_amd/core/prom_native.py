@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from krr_amd.core.packing import PackedSeries
+from krr_amd.core.packing import PackedSeries, pod_fields
 
 _HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("KRR_HOST_LIB", os.path.join(_HERE, "lib", "libkrr_host.so"))
@@ -197,9 +197,9 @@ def pack_query_range_bodies(per_object_bodies: Sequence[Sequence[bytes]], *, wan
         values = alloc(n) if alloc is not None else np.empty(n, dtype=np.float64)
         offsets = np.empty(n_obj + 1, dtype=np.int64)
         ts = np.empty(n, dtype=np.float64) if want_timestamps else None
-        counts = np.empty(max(nb, 1), dtype=np.int64) if return_pod_counts else None
+        counts = np.empty(max(nb, 1), dtype=np.int64)
         rc = lib.krr_pack_copy(h, _ptr(values), _ptr(offsets), _ptr(ts) if ts is not None else None,
-                               _ptr(counts) if counts is not None else None, int(threads))
+                               _ptr(counts), int(threads))
         if rc != KRR_PACK_OK:
             raise PrometheusResponseError(rc, "krr_pack_copy failed")
         max_len = int(lib.krr_pack_max_len(h))
@@ -207,9 +207,14 @@ def pack_query_range_bodies(per_object_bodies: Sequence[Sequence[bytes]], *, wan
         if h:
             lib.krr_pack_free(h)
     series = PackedSeries(values, offsets, max_len)
+    # the pod boundaries: the kept pods (a dropped or sample-less body is no pod segment)
+    counts = counts[:nb]
+    keep = counts > 0
+    series.pod_offsets, series.pod_groups = pod_fields(
+        counts[keep], np.bincount(obj_a[:nb][keep], minlength=n_obj) if nb else np.zeros(n_obj, dtype=np.int64))
     out: list = [series]
     if want_timestamps:
         out.append(ts)
     if return_pod_counts:
-        out.append(counts[:nb])
+        out.append(counts)
     return out[0] if len(out) == 1 else tuple(out)

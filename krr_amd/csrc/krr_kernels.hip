@@ -2823,6 +2823,96 @@ __global__ __launch_bounds__(256) void k_pack_records(int64_t S, const double* _
     reinterpret_cast<longlong2*>(rec)[2 * s + 1] = b;
 }
 
+// ------------------------------ GROUP MAX ----------------------------------
+// krr_group_max: per group (an object) the first maximal item (a pod's percentile) of its
+// contiguous items, with np.max's NaN propagation; the fold of cpu_aggregation = "pods_max".
+// One wave per group, the lanes striding its items; each lane keeps its best (order key,
+// index) pair — indices ascend within a lane, so only a strictly larger key replaces it —
+// and two wave reductions (max key, then min index among the lanes holding it) keep the
+// lowest index among equal keys.  -0.0 and +0.0 share a key (float ==); the winner's own
+// bits are read back.  Lane 0 writes with ordinary stores.
+struct OpOr32 {
+    __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a | b; }
+};
+
+struct GroupMaxArgs {
+    int64_t G;              // groups
+    const int64_t* goffs;   // [G + 1] into the items
+    int32_t rows;           // value / flag rows (percentiles); the counts are shared
+    int64_t N;              // items per row
+    const double* in_v;     // [rows * N]
+    const int64_t* in_n;    // [N]
+    const uint32_t* in_f;   // [rows * N]
+    double* out_v;          // [rows * G]
+    int64_t* out_n;         // [G]
+    uint32_t* out_f;        // [rows * G]
+    int64_t* out_arg;       // [rows * G] or null: the winning item's index within its group
+    int64_t* rec;           // optional 32-B records, CPU half (rows == 1)
+};
+
+__global__ __launch_bounds__(64) void k_group_max(GroupMaxArgs A) {
+    const int lane = threadIdx.x;
+    constexpr int64_t kNone = 0x7FFFFFFFFFFFFFFFll;
+    for (int64_t g = blockIdx.x; g < A.G; g += gridDim.x) {
+        const int64_t a0 = A.goffs[g];
+        int64_t a = a0, e = A.goffs[g + 1];
+        a = a < 0 ? 0 : a;  // offsets past the items read nothing
+        e = e > A.N ? A.N : e;
+#pragma unroll 1
+        for (int r = 0; r < A.rows; ++r) {
+            const double* v = A.in_v + (int64_t)r * A.N;
+            const uint32_t* f = A.in_f + (int64_t)r * A.N;
+            uint64_t best = 0;  // below every non-NaN value's key
+            int64_t best_i = kNone, bad_i = kNone;
+            uint64_t cnt = 0;
+            uint32_t fo = 0, have = 0;
+            for (int64_t i = a + lane; i < e; i += kWave) {
+                const uint32_t fl = f[i];
+                if (fl & KRR_FLAG_EMPTY) continue;
+                have = 1;
+                fo |= fl;
+                cnt += (uint64_t)A.in_n[i];
+                const uint64_t u = dbits(v[i]);
+                if ((fl & (KRR_FLAG_NAN | KRR_FLAG_CAPACITY)) || is_nan_bits(u)) {
+                    if (bad_i == kNone) bad_i = i;
+                } else {
+                    const uint64_t key = okey(is_zero_bits(u) ? 0ull : u);
+                    if (key > best) {
+                        best = key;
+                        best_i = i;
+                    }
+                }
+            }
+            const bool any = ballot(have != 0) != 0;
+            const uint64_t kmax = wave_max_u64(best);
+            const int64_t win = (int64_t)wave_min_u64(best == kmax ? (uint64_t)best_i : (uint64_t)kNone);
+            const int64_t bad = (int64_t)wave_min_u64((uint64_t)bad_i);
+            const uint64_t n = lane_bcast64(wave_scan64(cnt, 0ull, OpAdd64{}), kWave - 1);
+            const uint32_t flags = lane_bcast32(wave_scan32(fo, 0u, OpOr32{}), kWave - 1);
+            if (lane == 0) {
+                double result = bitsd(kQuietNaN);
+                uint32_t of = KRR_FLAG_EMPTY;
+                int64_t arg = -1;
+                if (any) {
+                    of = flags;
+                    if (bad != kNone) {
+                        arg = bad - a0;
+                    } else if (win != kNone) {  // always: a contributing item is bad or has a key > 0
+                        result = v[win];
+                        arg = win - a0;
+                    }
+                }
+                const int64_t o = (int64_t)r * A.G + g;
+                A.out_v[o] = result;
+                A.out_f[o] = of;
+                if (A.out_arg) A.out_arg[o] = arg;
+                if (r == 0) A.out_n[g] = (int64_t)n;
+                put_record(A.rec, g, 0, result, n, of);
+            }
+        }
+    }
+}
+
 // Largest segment length (for planning when the caller did not pass it).
 __global__ void k_maxlen(const int64_t* __restrict__ offs, int64_t S, unsigned long long* out) {
     uint64_t m = 0;
@@ -3821,6 +3911,87 @@ int krr_simple_run_records(krr_ctx* ctx, const krr_series* cpu, const krr_series
                                   mem_flags, records, nullptr, nullptr, 0, stream);
 }
 
+// The fused launch behind krr_simple_run_forward and krr_simple_run_pods: cpu holds S_cpu
+// segments and mem S_mem, and nothing in k_simple needs the two counts to be equal (work
+// items b < S_cpu are CPU segments, the rest memory segments).  cpu_rec / mem_rec: the
+// records whose CPU / memory half the launch writes (the same buffer for one CPU segment
+// per object; cpu_rec NULL when the CPU segments are pods, whose fold writes that half).
+static int simple_run_counts(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,
+                             const krr_percentile_params* params, double* cpu_value, int64_t* cpu_count,
+                             uint32_t* cpu_flags, double* mem_value, int64_t* mem_count, uint32_t* mem_flags,
+                             int64_t* cpu_rec, int64_t* mem_rec, const void* forward_src, void* forward_dst,
+                             int64_t forward_bytes, void* stream) {
+    const int64_t S_cpu = cpu->n_segments, S_mem = mem->n_segments;
+    int rc = KRR_OK;
+    const int64_t fwd_units = forward_bytes / 16;
+    const bool unfused = S_cpu == 0 || (params->mode == KRR_PCT_REF_INDEX && !cpu->gaps_are_nan);
+    if (fwd_units > 0 && (S_mem == 0 || unfused)) {
+        // no fused launch to ride on: a plain copy on the stream
+        DeviceGuard g(ctx->device);
+        if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+        KRR_HIP(ctx, hipMemcpyAsync(forward_dst, forward_src, (size_t)forward_bytes, hipMemcpyDefault,
+                                    (hipStream_t)stream));
+    }
+    if (S_mem == 0) return KRR_OK;
+    if (unfused) {
+        // compact REF_INDEX is one gather per segment: nothing to fuse with (and a fleet
+        // without one pod has no CPU segment at all)
+        rc = krr_segmented_percentile(ctx, cpu, params, cpu_value, cpu_count, cpu_flags, stream);
+        if (rc) return rc;
+        DeviceGuard g(ctx->device);
+        if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+        // with CPU records the pack pass writes both halves; else k_max writes the memory half
+        const MaxArgs M = max_args(mem, mem_value, mem_count, mem_flags, cpu_rec ? nullptr : mem_rec);
+        hipLaunchKernelGGL(k_max, dim3(grid_for(S_mem)), dim3(64), 0, (hipStream_t)stream, M);
+        KRR_HIP(ctx, hipGetLastError());
+        if (cpu_rec)
+            rc = krr_pack_records(ctx, S_mem, cpu_value, cpu_count, cpu_flags, mem_value, mem_count, mem_flags,
+                                  cpu_rec, stream);
+        return rc;
+    }
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    hipStream_t st = (hipStream_t)stream;
+    MaxArgs M = max_args(mem, mem_value, mem_count, mem_flags, mem_rec);
+    if (fwd_units > 0) {
+        M.fwd_src = (const double2*)forward_src;
+        M.fwd_dst = (double2*)forward_dst;
+        M.fwd_units = fwd_units;
+        M.fwd_items = ((fwd_units + kFwdItemUnits - 1) / kFwdItemUnits + 7) & ~(int64_t)7;
+    }
+    const int64_t items = M.fwd_items + S_cpu + S_mem;
+    RefArgs R{cpu->values, cpu->offsets, S_cpu, params->p_num, params->p_den, params->k_table, params->k_table_len,
+              cpu_value, cpu_count, cpu_flags, cpu_rec};
+    SelectArgs A{};
+    const bool fwd = M.fwd_items > 0;
+    if (params->mode == KRR_PCT_REF_INDEX) {
+        rc = check_table(ctx, cpu, params, st);
+        if (rc) return rc;
+        if (fwd) hipLaunchKernelGGL((k_simple<CPU_REF_GAPS, true>), dim3(grid_for(items)), dim3(64), 0, st, A, R, M);
+        else hipLaunchKernelGGL((k_simple<CPU_REF_GAPS>), dim3(grid_for(items)), dim3(64), 0, st, A, R, M);
+    } else {
+        size_t lds = 0;
+        rc = plan_select(ctx, cpu, params, st, cpu_value, cpu_count, cpu_flags, &A, &lds, true);
+        if (rc) return rc;
+        A.rec = cpu_rec;
+        const dim3 g(grid_for(items)), b(64);
+        if (A.cap) {
+            if (fwd) hipLaunchKernelGGL((k_simple<CPU_SELECT, true>), g, b, lds, st, A, R, M);
+            else hipLaunchKernelGGL((k_simple<CPU_SELECT>), g, b, lds, st, A, R, M);
+        } else if (A.wcap == kWselCapLong) {
+            if (fwd) hipLaunchKernelGGL((k_simple<CPU_HSELECT_LONG, true>), g, b, lds, st, A, R, M);
+            else hipLaunchKernelGGL((k_simple<CPU_HSELECT_LONG>), g, b, lds, st, A, R, M);
+        } else {
+            if (fwd) hipLaunchKernelGGL((k_simple<CPU_HSELECT, true>), g, b, lds, st, A, R, M);
+            else hipLaunchKernelGGL((k_simple<CPU_HSELECT>), g, b, lds, st, A, R, M);
+        }
+        KRR_HIP(ctx, hipGetLastError());
+        return launch_fallback(ctx, A, S_cpu, st);  // the misses are CPU segments: their count
+    }
+    KRR_HIP(ctx, hipGetLastError());
+    return KRR_OK;
+}
+
 int krr_simple_run_forward(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,
                            const krr_percentile_params* params, double* cpu_value, int64_t* cpu_count,
                            uint32_t* cpu_flags, double* mem_value, int64_t* mem_count, uint32_t* mem_flags,
@@ -3841,65 +4012,69 @@ int krr_simple_run_forward(krr_ctx* ctx, const krr_series* cpu, const krr_series
     const int64_t S = cpu->n_segments;
     if (S > 0 && (!cpu_value || !cpu_count || !cpu_flags || !mem_value || !mem_count || !mem_flags))
         return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
-    const int64_t fwd_units = forward_bytes / 16;
-    if (fwd_units > 0 && (S == 0 || (params->mode == KRR_PCT_REF_INDEX && !cpu->gaps_are_nan))) {
-        // no fused launch to ride on: a plain copy on the stream
-        DeviceGuard g(ctx->device);
-        if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-        KRR_HIP(ctx, hipMemcpyAsync(forward_dst, forward_src, (size_t)forward_bytes, hipMemcpyDefault,
-                                    (hipStream_t)stream));
-    }
-    if (S == 0) return KRR_OK;
-    if (params->mode == KRR_PCT_REF_INDEX && !cpu->gaps_are_nan) {
-        // compact REF_INDEX is one gather per segment: nothing to fuse with
-        rc = krr_segmented_percentile(ctx, cpu, params, cpu_value, cpu_count, cpu_flags, stream);
-        if (!rc) rc = krr_segmented_max(ctx, mem, mem_value, mem_count, mem_flags, stream);
-        if (!rc && records)
-            rc = krr_pack_records(ctx, S, cpu_value, cpu_count, cpu_flags, mem_value, mem_count, mem_flags,
-                                  records, stream);
-        return rc;
-    }
+    return simple_run_counts(ctx, cpu, mem, params, cpu_value, cpu_count, cpu_flags, mem_value, mem_count, mem_flags,
+                             records, records, forward_src, forward_dst, forward_bytes, stream);
+}
+
+int krr_group_max(krr_ctx* ctx, int64_t n_groups, const int64_t* group_offsets, int32_t n_rows, int64_t n_items,
+                  const double* in_value, const int64_t* in_count, const uint32_t* in_flags, double* out_value,
+                  int64_t* out_count, uint32_t* out_flags, int64_t* out_arg, int64_t* records, void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    if (n_groups < 0 || n_items < 0 || n_rows < 1 || n_rows > KRR_MAX_PERCENTILES)
+        return set_err(ctx, KRR_E_INVALID, "group_max: negative sizes or n_rows outside [1, %s%lld]", "",
+                       (long long)KRR_MAX_PERCENTILES);
+    if (records && n_rows != 1) return set_err(ctx, KRR_E_INVALID, "group_max: records take one row%s", "");
+    if (n_groups == 0) return KRR_OK;
+    if (!group_offsets || !out_value || !out_count || !out_flags ||
+        (n_items > 0 && (!in_value || !in_count || !in_flags)))
+        return set_err(ctx, KRR_E_INVALID, "group_max: null pointer%s", "");
     DeviceGuard g(ctx->device);
     if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-    hipStream_t st = (hipStream_t)stream;
-    MaxArgs M = max_args(mem, mem_value, mem_count, mem_flags, records);
-    if (fwd_units > 0) {
-        M.fwd_src = (const double2*)forward_src;
-        M.fwd_dst = (double2*)forward_dst;
-        M.fwd_units = fwd_units;
-        M.fwd_items = ((fwd_units + kFwdItemUnits - 1) / kFwdItemUnits + 7) & ~(int64_t)7;
-    }
-    const int64_t items = M.fwd_items + 2 * S;
-    RefArgs R{cpu->values, cpu->offsets, S, params->p_num, params->p_den, params->k_table, params->k_table_len,
-              cpu_value, cpu_count, cpu_flags, records};
-    SelectArgs A{};
-    const bool fwd = M.fwd_items > 0;
-    if (params->mode == KRR_PCT_REF_INDEX) {
-        rc = check_table(ctx, cpu, params, st);
-        if (rc) return rc;
-        if (fwd) hipLaunchKernelGGL((k_simple<CPU_REF_GAPS, true>), dim3(grid_for(items)), dim3(64), 0, st, A, R, M);
-        else hipLaunchKernelGGL((k_simple<CPU_REF_GAPS>), dim3(grid_for(items)), dim3(64), 0, st, A, R, M);
-    } else {
-        size_t lds = 0;
-        rc = plan_select(ctx, cpu, params, st, cpu_value, cpu_count, cpu_flags, &A, &lds, true);
-        if (rc) return rc;
-        A.rec = records;
-        const dim3 g(grid_for(items)), b(64);
-        if (A.cap) {
-            if (fwd) hipLaunchKernelGGL((k_simple<CPU_SELECT, true>), g, b, lds, st, A, R, M);
-            else hipLaunchKernelGGL((k_simple<CPU_SELECT>), g, b, lds, st, A, R, M);
-        } else if (A.wcap == kWselCapLong) {
-            if (fwd) hipLaunchKernelGGL((k_simple<CPU_HSELECT_LONG, true>), g, b, lds, st, A, R, M);
-            else hipLaunchKernelGGL((k_simple<CPU_HSELECT_LONG>), g, b, lds, st, A, R, M);
-        } else {
-            if (fwd) hipLaunchKernelGGL((k_simple<CPU_HSELECT, true>), g, b, lds, st, A, R, M);
-            else hipLaunchKernelGGL((k_simple<CPU_HSELECT>), g, b, lds, st, A, R, M);
-        }
-        KRR_HIP(ctx, hipGetLastError());
-        return launch_fallback(ctx, A, S, st);
-    }
+    const GroupMaxArgs A{n_groups, group_offsets, n_rows, n_items, in_value, in_count, in_flags,
+                         out_value, out_count, out_flags, out_arg, records};
+    const int64_t grid = n_groups < 65536 ? n_groups : 65536;  // grid-stride past that
+    hipLaunchKernelGGL(k_group_max, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, A);
     KRR_HIP(ctx, hipGetLastError());
     return KRR_OK;
+}
+
+int krr_simple_run_pods(krr_ctx* ctx, const krr_series* cpu_pods, const int64_t* pod_groups, const krr_series* mem,
+                        const krr_percentile_params* params, double* pod_value, int64_t* pod_count,
+                        uint32_t* pod_flags, double* cpu_value, int64_t* cpu_count, uint32_t* cpu_flags,
+                        int64_t* cpu_pod, double* mem_value, int64_t* mem_count, uint32_t* mem_flags,
+                        int64_t* records, void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    if (!cpu_pods || !mem || !pod_groups) return set_err(ctx, KRR_E_INVALID, "null series or pod_groups%s", "");
+    int rc = check_series(ctx, cpu_pods);
+    if (!rc) rc = check_series(ctx, mem);
+    if (!rc) rc = check_params(ctx, params);
+    if (rc) return rc;
+    const int64_t n_pods = cpu_pods->n_segments, n_objects = mem->n_segments;
+    if (n_pods > 0 && (!pod_value || !pod_count || !pod_flags)) return set_err(ctx, KRR_E_INVALID, "null pod outputs%s", "");
+    if (n_objects > 0 && (!cpu_value || !cpu_count || !cpu_flags || !mem_value || !mem_count || !mem_flags))
+        return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+    {
+        // pod_groups must span the pod segments: [0] == 0 and [n_objects] == n_pods (two words
+        // read back on the stream, which orders them after the caller's upload)
+        DeviceGuard g(ctx->device);
+        if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+        hipStream_t st = (hipStream_t)stream;
+        int64_t ends[2] = {0, 0};
+        KRR_HIP(ctx, hipMemcpyAsync(&ends[0], pod_groups, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        KRR_HIP(ctx, hipMemcpyAsync(&ends[1], pod_groups + n_objects, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        KRR_HIP(ctx, hipStreamSynchronize(st));
+        if (ends[0] != 0 || ends[1] != n_pods)
+            return set_err(ctx, KRR_E_INVALID, "pod_groups must span the pod segments: it ends at %s%lld", "",
+                           (long long)ends[1]);
+    }
+    if (n_objects == 0) return KRR_OK;
+    // the existing fused launch over n_pods CPU segments and n_objects memory segments (the
+    // memory side writes its record half), then the fold on the same stream (the CPU half)
+    rc = simple_run_counts(ctx, cpu_pods, mem, params, pod_value, pod_count, pod_flags, mem_value, mem_count,
+                           mem_flags, nullptr, records, nullptr, nullptr, 0, stream);
+    if (rc) return rc;
+    return krr_group_max(ctx, n_objects, pod_groups, 1, n_pods, pod_value, pod_count, pod_flags, cpu_value,
+                         cpu_count, cpu_flags, cpu_pod, records, stream);
 }
 
 int krr_simple_run_host(krr_ctx* ctx, const double* cpu_values, const int64_t* cpu_offsets,

@@ -70,14 +70,18 @@ class PrometheusHTTPError(RuntimeError):
     reference lets it abort the run: nothing in prometheus.py:108-155 catches it)."""
 
 
-def hip_strategy(reference_strategy: Any) -> Optional[SimpleStrategy]:
+def hip_strategy(reference_strategy: Any, cpu_aggregation: Optional[str] = None) -> Optional[SimpleStrategy]:
     """The HIP-backed SimpleStrategy equivalent to the reference's, or None for any other
-    strategy (custom plugins keep the reference's per-object ``run()``)."""
+    strategy (custom plugins keep the reference's per-object ``run()``).  ``cpu_aggregation``
+    (``install``'s switch; the reference's settings have no such field): "pods_max" takes the
+    max over an object's pods of each pod's percentile instead of the flat percentile."""
     cls = type(reference_strategy)
     if (cls.__module__, cls.__name__) != REFERENCE_SIMPLE:
         return None
     settings = reference_strategy.settings
     explicit = {name: getattr(settings, name) for name in getattr(settings, "__fields_set__", ())}
+    if cpu_aggregation not in (None, "concat"):  # the default stays an unset field
+        explicit["cpu_aggregation"] = cpu_aggregation
     return SimpleStrategy(SimpleStrategySettings(**explicit))
 
 
@@ -95,7 +99,7 @@ def _options(runner: Any) -> dict:
 async def gather_objects_recommendations(runner: Any, objects: Sequence[Any]) -> list:
     """Drop-in body of the reference's ``Runner._gather_objects_recommendations``."""
     RefResourceType, RefResourceAllocations = _reference_types(runner)
-    strategy = hip_strategy(runner._strategy)
+    strategy = hip_strategy(runner._strategy, _options(runner).get("cpu_aggregation"))
     if strategy is None:  # the reference's own per-object path (runner.py:109-120)
         original = getattr(type(runner), _ORIGINAL_ATTR, None)
         if original is not None:
@@ -279,7 +283,7 @@ async def collect_result(runner: Any):
     runner.debug(f'Using clusters: {clusters if clusters is not None else "inner cluster"}')
     objects = await runner._k8s_loader.list_scannable_objects(clusters)
     models = sys.modules[sys.modules[type(runner).__module__].Result.__module__]
-    strategy = hip_strategy(runner._strategy)
+    strategy = hip_strategy(runner._strategy, _options(runner).get("cpu_aggregation"))
     if strategy is not None and getattr(type(runner)._gather_objects_recommendations, _PATCHED_ATTR, False):
         # the gather is this module's: its ResourceAllocations would only be read by the scan, so
         # the rounded values go straight into it (fast_round.result_batch)
@@ -299,14 +303,17 @@ async def collect_result(runner: Any):
 
 
 def install(runner_cls: Any = None, *, loader: str = "reference", scan: str = "reference",
-            parser: str = "device") -> Any:
+            parser: str = "device", cpu_aggregation: str = "concat") -> Any:
     """Route ``runner_cls._gather_objects_recommendations`` (default: the reference's
     ``robusta_krr.core.runner.Runner``) through ``gather_objects_recommendations``, loading
     histories with ``loader`` (see the module docstring), and with ``scan="fleet"`` also
     ``_collect_result`` through ``collect_result``.  ``parser`` (loader="bodies"): "device"
     parses the raw bodies on the MI355X (krr_amd.core.device_pack), "host" with the native
     host packer, "hybrid" both at once on disjoint object ranges
-    (``BatchedRunner.pack_hybrid``; loader="grouped" parses as "device").  Calling it again
+    (``BatchedRunner.pack_hybrid``; loader="grouped" parses as "device").
+    ``cpu_aggregation="pods_max"``: CPU is the max over an object's pods of each pod's
+    percentile (SimpleStrategySettings.cpu_aggregation); it needs a loader that keeps the pod
+    boundaries — "reference", or "bodies" with parser="host".  Calling it again
     changes the switches;
     ``uninstall`` restores the reference's methods.  Returns the class."""
     if loader not in LOADERS:
@@ -315,6 +322,8 @@ def install(runner_cls: Any = None, *, loader: str = "reference", scan: str = "r
         raise ValueError(f"scan must be one of {SCANS}")
     if parser not in ("device", "host", "hybrid"):
         raise ValueError("parser must be 'device', 'host' or 'hybrid'")
+    if cpu_aggregation not in ("concat", "pods_max"):
+        raise ValueError("cpu_aggregation must be 'concat' or 'pods_max'")
     if runner_cls is None:
         from robusta_krr.core.runner import Runner as runner_cls  # the reference, in its own process
     if getattr(runner_cls, _ORIGINAL_ATTR, None) is None:
@@ -336,7 +345,8 @@ def install(runner_cls: Any = None, *, loader: str = "reference", scan: str = "r
     elif scan == "reference" and getattr(runner_cls, _ORIGINAL_COLLECT_ATTR, None) is not None:
         runner_cls._collect_result = getattr(runner_cls, _ORIGINAL_COLLECT_ATTR)
         setattr(runner_cls, _ORIGINAL_COLLECT_ATTR, None)
-    setattr(runner_cls, _OPTIONS_ATTR, {"loader": loader, "scan": scan, "parser": parser})
+    setattr(runner_cls, _OPTIONS_ATTR, {"loader": loader, "scan": scan, "parser": parser,
+                                       "cpu_aggregation": cpu_aggregation})
     return runner_cls
 
 

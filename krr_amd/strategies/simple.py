@@ -50,6 +50,11 @@ class PercentileMode(str, enum.Enum):
     LINEAR = "linear"
 
 
+class CpuAggregation(str, enum.Enum):
+    CONCAT = "concat"        # one percentile over the object's pods concatenated (KRR 1.0.0)
+    PODS_MAX = "pods_max"    # the max over the pods of each pod's percentile (later KRR)
+
+
 class SimpleStrategySettings(StrategySettings):
     cpu_percentile: Decimal = pd.Field(
         99, gt=0, le=100, description="The percentile to use for the CPU recommendation."
@@ -60,6 +65,11 @@ class SimpleStrategySettings(StrategySettings):
     percentile_mode: PercentileMode = pd.Field(
         PercentileMode.REF_INDEX,
         description="CPU percentile rule: ref_index (reference KRR 1.0.0), sorted_lower, or linear (numpy).",
+    )
+    cpu_aggregation: CpuAggregation = pd.Field(
+        CpuAggregation.CONCAT,
+        description="CPU over an object's pods: concat (one percentile over the pods' samples concatenated, "
+                    "reference KRR 1.0.0) or pods_max (the max over the pods of each pod's percentile).",
     )
     device: int = pd.Field(0, ge=0, description="HIP device that runs the kernels.")
 
@@ -80,10 +90,31 @@ class SimpleStrategySettings(StrategySettings):
         with decimal.localcontext(reference_context()):
             return Decimal(1 + self.memory_buffer_percentage / 100)
 
+    def aggregation(self) -> str:
+        # settings built by .construct() (simple_limit) carry no field: the default
+        return CpuAggregation(getattr(self, "cpu_aggregation", CpuAggregation.CONCAT)).value
+
     def run_fleet(self, fleet: PackedFleet, device: Optional[int] = None) -> RawResults:
+        """The kernel pass over a packed fleet.  ``cpu_aggregation`` "pods_max": each pod's
+        percentile (any ``percentile_mode``) and the max over the object's pods, first maximal
+        pod, one fused launch plus the fold (krr_simple_run_pods); the fleet's CPU series must
+        carry pod boundaries (every host packer writes them; the device packer does not:
+        ValueError).  NaN samples among the CPU values stay out of contract, as on the flat
+        path: a pod's KRR_FLAG_NAN is folded into the object's flags and ``cpu_from_raw``
+        applies its rule with the folded count."""
         params = self.params()
-        raw = default_engine(self.device if device is None else device).run_packed(fleet, params)
-        if fleet.cpu.exact is not None or fleet.mem.exact is not None:
+        agg = self.aggregation()
+        engine = default_engine(self.device if device is None else device)
+        exact = fleet.cpu.exact is not None or fleet.mem.exact is not None
+        if agg == CpuAggregation.PODS_MAX.value:
+            raw = engine.run_packed(fleet, params, aggregation=agg, return_pods=exact)
+            if exact and fleet.n_objects:
+                from krr_amd.core.exact import resolve_pods
+
+                resolve_pods(fleet, raw, params)
+            return raw
+        raw = engine.run_packed(fleet, params)
+        if exact:
             from krr_amd.core.exact import resolve
 
             resolve(fleet, raw, params)
@@ -91,7 +122,11 @@ class SimpleStrategySettings(StrategySettings):
 
     def run_fleet_records(self, fleet: PackedFleet, device: Optional[int] = None):
         """One kernel pass over a fleet shard -> int64 [S, 4] device records (multi-GPU path)."""
-        return default_engine(self.device if device is None else device).run_packed_records(fleet, self.params())
+        engine = default_engine(self.device if device is None else device)
+        agg = self.aggregation()
+        if agg == CpuAggregation.PODS_MAX.value:
+            return engine.run_packed_records(fleet, self.params(), aggregation=agg)
+        return engine.run_packed_records(fleet, self.params())
 
     def _run_single(self, history: HistoryData) -> RawResults:
         return self.run_fleet(pack_histories([history]))
