@@ -319,6 +319,37 @@ int krr_simple_run_pods(krr_ctx* ctx, const krr_series* cpu_pods, const int64_t*
                         int64_t* cpu_pod, double* mem_value, int64_t* mem_count, uint32_t* mem_flags,
                         int64_t* records, void* stream);
 
+/* krr_simple_run_pods for a set of percentiles (simple_limit under cpu_aggregation =
+ * "pods_max": request and limit per pod, each the max over the pods): params as for
+ * krr_simple_run_multi (1 <= n_params = P <= KRR_MAX_PERCENTILES entries of one mode, each
+ * entry's k_table checked against the POD series' longest segment), the series and pod_groups
+ * as for krr_simple_run_pods.  Row j of pod_value / pod_flags [P * n_pods] and of cpu_value /
+ * cpu_flags / cpu_pod [P * n_objects] (cpu_pod may be NULL) equals, bit for bit, what
+ * krr_simple_run_pods writes for params[j] alone — each row has its own winning pod;
+ * pod_count [n_pods], cpu_count [n_objects] and the memory outputs are shared and equal its
+ * too.  No records: a 32-byte record holds one CPU value.  n_params == 1 is
+ * krr_simple_run_pods with NULL records.
+ *
+ * The launch is planned by the pod series' max_segment_len, so a set shares one pass here
+ * (krr_multi_plan at the longest POD) that would not over the objects' concatenated series:
+ * then one launch streams every value once — the pod segments answer all P percentiles from
+ * one candidate buffer, the memory segments follow.  Compact REF_INDEX gathers
+ * (krr_segmented_percentiles) and takes the memory max apart; a set that does not share runs
+ * params[0] in krr_simple_run_pods' fused launch and one krr_segmented_percentile over the
+ * pods per further entry; a fleet without one pod segment runs the memory max alone.  One
+ * krr_group_max with n_rows = P follows on the stream in every case (without pods: every row
+ * KRR_FLAG_EMPTY, quiet NaN, cpu_pod -1).  n_objects == 0 writes nothing.  Synchronises the
+ * stream once (the pod_groups check).
+ * KRR_E_INVALID: n_params outside [1, KRR_MAX_PERCENTILES], mixed modes, a null pointer,
+ * pod_groups not spanning the pod segments; nothing is launched then. */
+int krr_simple_run_pods_multi(krr_ctx* ctx, const krr_series* cpu_pods, const int64_t* pod_groups,
+                              const krr_series* mem, const krr_percentile_params* params, int32_t n_params,
+                              double* pod_value /* [P*n_pods] */, int64_t* pod_count /* [n_pods] */,
+                              uint32_t* pod_flags /* [P*n_pods] */, double* cpu_value /* [P*n_objects] */,
+                              int64_t* cpu_count /* [n_objects] */, uint32_t* cpu_flags /* [P*n_objects] */,
+                              int64_t* cpu_pod /* [P*n_objects] or NULL */, double* mem_value, int64_t* mem_count,
+                              uint32_t* mem_flags, void* stream);
+
 /* Counters of the ctx since krr_create (synchronises the device): segments whose
  * one-pass window select (wselect) missed and were finished by the two-pass
  * histogram select.  Diagnostic: results are exact either way. */

@@ -91,6 +91,7 @@ EXPORTED_SYMBOLS = (
     "krr_simple_run_multi",
     "krr_group_max",
     "krr_simple_run_pods",
+    "krr_simple_run_pods_multi",
     "krr_get_stats",
     "krr_comm_unique_id",
     "krr_comm_init",
@@ -317,6 +318,8 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_group_max.restype = ctypes.c_int
         lib.krr_simple_run_pods.argtypes = [vp, sp, vp, sp, pp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_pods.restype = ctypes.c_int
+        lib.krr_simple_run_pods_multi.argtypes = [vp, sp, vp, sp, pp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_simple_run_pods_multi.restype = ctypes.c_int
         lib.krr_get_stats.argtypes = [vp, ctypes.POINTER(i64)]
         lib.krr_get_stats.restype = ctypes.c_int
         lib.krr_comm_unique_id.argtypes = [vp, vp]
@@ -600,6 +603,32 @@ class Context:
             cpu_pod.data_ptr() if cpu_pod is not None else None,
             out["mem_value"].data_ptr(), out["mem_count"].data_ptr(), out["mem_flags"].data_ptr(),
             records.data_ptr() if records is not None else None, self._stream(stream)))
+
+    def simple_run_pods_multi(self, cpu_pods: KrrSeries, pod_groups, mem: KrrSeries, params_list, out: dict,
+                              stream=None) -> None:
+        """simple_run_pods for several CPU percentiles (krr_simple_run_pods_multi): out as for
+        simple_run_pods with cpu_value float64, cpu_flags int32 and (optional) cpu_pod int64
+        [P, S], pod_value float64 and pod_flags int32 [P, n_pods], row j for params_list[j];
+        cpu_count [S], pod_count [n_pods] and the memory tensors [S] are shared.  No records: a
+        record holds one CPU value.  Synchronises the stream once (the pod_groups check)."""
+        P, S, n_pods = len(params_list), mem.n_segments, cpu_pods.n_segments
+        _check_tensor(pod_groups, "int64", S + 1)
+        for k, dt, m in (("cpu_value", "float64", P * S), ("cpu_count", "int64", S), ("cpu_flags", "int32", P * S),
+                         ("mem_value", "float64", S), ("mem_count", "int64", S), ("mem_flags", "int32", S),
+                         ("pod_value", "float64", P * n_pods), ("pod_count", "int64", n_pods),
+                         ("pod_flags", "int32", P * n_pods)):
+            _check_tensor(out[k], dt, m)
+        cpu_pod = out.get("cpu_pod")
+        if cpu_pod is not None:
+            _check_tensor(cpu_pod, "int64", P * S)
+        arr = self._param_array(params_list, cpu_pods)
+        self._check(self._lib.krr_simple_run_pods_multi(
+            self._h, ctypes.byref(cpu_pods), pod_groups.data_ptr(), ctypes.byref(mem), arr, P,
+            out["pod_value"].data_ptr(), out["pod_count"].data_ptr(), out["pod_flags"].data_ptr(),
+            out["cpu_value"].data_ptr(), out["cpu_count"].data_ptr(), out["cpu_flags"].data_ptr(),
+            cpu_pod.data_ptr() if cpu_pod is not None else None,
+            out["mem_value"].data_ptr(), out["mem_count"].data_ptr(), out["mem_flags"].data_ptr(),
+            self._stream(stream)))
 
     def pack_records(self, out: dict, records, stream=None) -> None:
         """out: the six result tensors; records: int64 [S, 4] device tensor."""

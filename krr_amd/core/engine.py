@@ -285,18 +285,26 @@ class SimpleEngine:
         n = 1 if resident or nbytes <= 2 * self.chunk_bytes else -(-nbytes // self.chunk_bytes)
         return [(0, S)] if n == 1 else [(lo, hi) for lo, hi in fleet_shard_bounds(fleet, n) if hi > lo]
 
-    def run_packed_multi(self, fleet: PackedFleet, params_list) -> list:
+    def run_packed_multi(self, fleet: PackedFleet, params_list, aggregation: str = "concat",
+                         return_pods: bool = False) -> list:
         """Several CPU percentiles of a fleet (host- or device-packed) from one fused pass per
         chunk (krr_simple_run_multi): one RawResults per entry of ``params_list``, sharing the
         memory arrays and the CPU counts, so ``krr_amd.core.exact.resolve`` and
         ``cpu_from_raw`` work per percentile unchanged.  HistoryData segments of exactness
-        class >= 1 are located per percentile (``_locate_chunk``)."""
+        class >= 1 are located per percentile (``_locate_chunk``).  ``aggregation`` "pods_max":
+        every percentile per pod and its max over the object's pods (krr_simple_run_pods_multi;
+        the CPU series needs pod boundaries); ``return_pods`` then adds each percentile's
+        pod-level results (RawResults.pods, as run_packed's)."""
         import torch
 
         params_list = list(params_list)
+        if aggregation not in ("concat", "pods_max"):
+            raise ValueError(f"unknown cpu aggregation {aggregation!r}; expected 'concat' or 'pods_max'")
         if fleet.cpu.n_segments != fleet.mem.n_segments:
             raise ValueError("cpu and memory need one segment per object each")
         ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        if aggregation == "pods_max":
+            return self._run_packed_multi_pods(fleet, params_list, return_pods)
         S, P = fleet.n_objects, len(params_list)
         if S == 0:
             return [_empty_results() for _ in range(P)]
@@ -329,6 +337,78 @@ class SimpleEngine:
         return [RawResults(host["cpu_value"][j], host["cpu_count"], host["cpu_flags"][j].view(np.uint32),
                            host["mem_value"], host["mem_count"], host["mem_flags"].view(np.uint32), locs[j])
                 for j in range(P)]
+
+    def _run_packed_multi_pods(self, fleet: PackedFleet, params_list: list, return_pods: bool) -> list:
+        """run_packed_multi under "pods_max": krr_simple_run_pods_multi per chunk over its pod
+        segments (``_run_chunks_pods`` for a set of percentiles), each chunk into [P, n] blocks
+        of its own.  The memory side is located once (every RawResults shares the answers); the
+        CPU side per percentile over the pod segments, under ``_run_chunks_pods``' condition."""
+        import torch
+
+        from krr_amd.core.packing import PackedSeries, pod_view
+
+        if fleet.cpu.pod_offsets is None or fleet.cpu.pod_groups is None:
+            pod_view(fleet.cpu)  # raises the ValueError that names the packer
+        S, P, n_pods = fleet.n_objects, len(params_list), fleet.cpu.n_pods
+        if S == 0:
+            return [_empty_results() for _ in range(P)]
+        ctx = self.context()
+        dev = torch.device("cuda", self.device)
+        obj_keys = (("cpu_value", torch.float64, P), ("cpu_count", torch.int64, 0), ("cpu_flags", torch.int32, P),
+                    ("cpu_pod", torch.int64, P), ("mem_value", torch.float64, 0), ("mem_count", torch.int64, 0),
+                    ("mem_flags", torch.int32, 0))
+        pod_keys = (("pod_value", torch.float64, P), ("pod_count", torch.int64, 0), ("pod_flags", torch.int32, P))
+
+        def block(keys, n):
+            return {k: torch.empty((rows, n) if rows else (n,), dtype=dt, device=dev) for k, dt, rows in keys}
+
+        locate = any(needs_locate(fleet, params) for params in params_list)
+        loc = {r: tuple(np.full(S, -1, dtype=np.int64) for _ in range(3)) for r in ("cpu", "mem")} if locate else None
+        pod_locs = [None] * P
+        if fleet.cpu.exact is not None:
+            for j, params in enumerate(params_list):
+                if params.mode == _native.KRR_PCT_SORTED_LOWER:
+                    pod_locs[j] = {"cpu": tuple(np.full(n_pods, -1, dtype=np.int64) for _ in range(3))}
+        with torch.cuda.device(self.device):
+            out = block(obj_keys, S)
+            pod_chunks = {k: [] for k, _, _ in pod_keys}
+            pod_lo = 0
+            for lo, hi, part, cs, ms in self._chunks(fleet):
+                view = pod_view(part.cpu)
+                po = torch.from_numpy(np.ascontiguousarray(view.offsets)).to(dev)
+                pg = torch.from_numpy(np.ascontiguousarray(part.cpu.pod_groups, dtype=np.int64)).to(dev)
+                pcs = ctx.series(cs._keep[0], po, max(view.max_len, 1), view.gaps_are_nan)
+                n = view.n_segments
+                whole = hi - lo == S
+                # a chunk's rows are not contiguous in the [P, S] outputs: its own [P, n] block
+                chunk = dict(out if whole else block(obj_keys, hi - lo), **block(pod_keys, n))
+                ctx.simple_run_pods_multi(pcs, pg, ms, params_list, chunk)
+                if not whole:
+                    for k, v in out.items():
+                        v[..., lo:hi] = chunk[k]
+                for k in pod_chunks:
+                    pod_chunks[k].append(chunk[k])
+                if locate:
+                    self._locate_chunk(ctx, part, cs, ms, params_list[0], chunk, loc, lo, names=("mem",))
+                for j, params in enumerate(params_list):
+                    if pod_locs[j] is not None and view.exact is not None:
+                        pod_out = {"cpu_value": chunk["pod_value"][j], "cpu_count": chunk["pod_count"],
+                                   "cpu_flags": chunk["pod_flags"][j]}
+                        self._locate_chunk(ctx, PackedFleet(view, PackedSeries(part.mem.values, part.mem.offsets, 0)),
+                                           pcs, ms, params, pod_out, pod_locs[j], pod_lo, names=("cpu",))
+                pod_lo += n
+            torch.cuda.current_stream(self.device).synchronize()
+        host = {k: v.cpu().numpy() for k, v in out.items()}
+        raws = [RawResults(host["cpu_value"][j], host["cpu_count"], host["cpu_flags"][j].view(np.uint32),
+                           host["mem_value"], host["mem_count"], host["mem_flags"].view(np.uint32), loc)
+                for j in range(P)]
+        if return_pods:
+            pod = {k: torch.cat(v, dim=-1).cpu().numpy() for k, v in pod_chunks.items()}  # S > 0: >= 1 chunk
+            for j, raw in enumerate(raws):
+                raw.pods = {"pod_value": pod["pod_value"][j], "pod_count": pod["pod_count"],
+                            "pod_flags": pod["pod_flags"][j].view(np.uint32), "cpu_pod": host["cpu_pod"][j],
+                            "locate": pod_locs[j]}
+        return raws
 
     def _locate_chunk(self, ctx, part: PackedFleet, cs, ms, params, out: dict, loc: dict, lo: int,
                       names=("cpu", "mem")) -> None:

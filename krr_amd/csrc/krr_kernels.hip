@@ -4038,6 +4038,23 @@ int krr_group_max(krr_ctx* ctx, int64_t n_groups, const int64_t* group_offsets, 
     return KRR_OK;
 }
 
+// pod_groups must span the pod segments: [0] == 0 and [n_objects] == n_pods (two words read
+// back on the stream, which orders them after the caller's upload; one synchronisation).
+static int check_pod_span(krr_ctx* ctx, const int64_t* pod_groups, int64_t n_objects, int64_t n_pods,
+                          void* stream) {
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    hipStream_t st = (hipStream_t)stream;
+    int64_t ends[2] = {0, 0};
+    KRR_HIP(ctx, hipMemcpyAsync(&ends[0], pod_groups, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    KRR_HIP(ctx, hipMemcpyAsync(&ends[1], pod_groups + n_objects, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    KRR_HIP(ctx, hipStreamSynchronize(st));
+    if (ends[0] != 0 || ends[1] != n_pods)
+        return set_err(ctx, KRR_E_INVALID, "pod_groups must span the pod segments: it ends at %s%lld", "",
+                       (long long)ends[1]);
+    return KRR_OK;
+}
+
 int krr_simple_run_pods(krr_ctx* ctx, const krr_series* cpu_pods, const int64_t* pod_groups, const krr_series* mem,
                         const krr_percentile_params* params, double* pod_value, int64_t* pod_count,
                         uint32_t* pod_flags, double* cpu_value, int64_t* cpu_count, uint32_t* cpu_flags,
@@ -4053,20 +4070,8 @@ int krr_simple_run_pods(krr_ctx* ctx, const krr_series* cpu_pods, const int64_t*
     if (n_pods > 0 && (!pod_value || !pod_count || !pod_flags)) return set_err(ctx, KRR_E_INVALID, "null pod outputs%s", "");
     if (n_objects > 0 && (!cpu_value || !cpu_count || !cpu_flags || !mem_value || !mem_count || !mem_flags))
         return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
-    {
-        // pod_groups must span the pod segments: [0] == 0 and [n_objects] == n_pods (two words
-        // read back on the stream, which orders them after the caller's upload)
-        DeviceGuard g(ctx->device);
-        if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-        hipStream_t st = (hipStream_t)stream;
-        int64_t ends[2] = {0, 0};
-        KRR_HIP(ctx, hipMemcpyAsync(&ends[0], pod_groups, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        KRR_HIP(ctx, hipMemcpyAsync(&ends[1], pod_groups + n_objects, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        KRR_HIP(ctx, hipStreamSynchronize(st));
-        if (ends[0] != 0 || ends[1] != n_pods)
-            return set_err(ctx, KRR_E_INVALID, "pod_groups must span the pod segments: it ends at %s%lld", "",
-                           (long long)ends[1]);
-    }
+    rc = check_pod_span(ctx, pod_groups, n_objects, n_pods, stream);
+    if (rc) return rc;
     if (n_objects == 0) return KRR_OK;
     // the existing fused launch over n_pods CPU segments and n_objects memory segments (the
     // memory side writes its record half), then the fold on the same stream (the CPU half)
@@ -4999,6 +5004,45 @@ int launch_multi(krr_ctx* ctx, const MultiArgs& A, const MaxArgs& M, const krr_m
     return KRR_OK;
 }
 
+// The multi launch behind krr_simple_run_multi and krr_simple_run_pods_multi, the counterpart of
+// simple_run_counts: cpu holds S_cpu segments (objects, or pods) and mem S_mem > 0, n_params
+// >= 2 checked entries; planned by cpu's max_segment_len.  Row j of cpu_value / cpu_flags is
+// [j * S_cpu ..).
+int simple_run_multi_counts(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,
+                            const krr_percentile_params* params, int32_t n_params, double* cpu_value,
+                            int64_t* cpu_count, uint32_t* cpu_flags, double* mem_value, int64_t* mem_count,
+                            uint32_t* mem_flags, void* stream) {
+    const int64_t S_cpu = cpu->n_segments;
+    // a fleet without one pod has no CPU segment at all: the memory half alone
+    if (S_cpu == 0) return krr_segmented_max(ctx, mem, mem_value, mem_count, mem_flags, stream);
+    int rc = KRR_OK;
+    if (params[0].mode == KRR_PCT_REF_INDEX && !cpu->gaps_are_nan) {
+        // compact REF_INDEX is P gathers per segment: nothing to fuse with
+        rc = krr_segmented_percentiles(ctx, cpu, params, n_params, cpu_value, cpu_count, cpu_flags, stream);
+        if (!rc) rc = krr_segmented_max(ctx, mem, mem_value, mem_count, mem_flags, stream);
+        return rc;
+    }
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    hipStream_t st = (hipStream_t)stream;
+    int64_t Lmax = 0;
+    krr_multi_plan_info plan;
+    rc = prepare_multi(ctx, cpu, params, n_params, st, &Lmax, &plan);
+    if (rc) return rc;
+    if (!plan.shared) {
+        // one percentile rides the fused launch with the memory half, the others are
+        // percentile-only passes: P + 1 half-passes instead of 2 P
+        rc = simple_run_counts(ctx, cpu, mem, &params[0], cpu_value, cpu_count, cpu_flags, mem_value, mem_count,
+                               mem_flags, nullptr, nullptr, nullptr, nullptr, 0, stream);
+        for (int32_t j = 1; j < n_params && !rc; ++j)
+            rc = krr_segmented_percentile(ctx, cpu, &params[j], cpu_value + (int64_t)j * S_cpu, cpu_count,
+                                          cpu_flags + (int64_t)j * S_cpu, stream);
+        return rc;
+    }
+    const MultiArgs A = multi_args(cpu, params, n_params, Lmax, plan, cpu_value, cpu_count, cpu_flags);
+    return launch_multi(ctx, A, max_args(mem, mem_value, mem_count, mem_flags, nullptr), plan, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -5065,31 +5109,38 @@ int krr_simple_run_multi(krr_ctx* ctx, const krr_series* cpu, const krr_series* 
     if (S == 0) return KRR_OK;
     if (!cpu_value || !cpu_count || !cpu_flags || !mem_value || !mem_count || !mem_flags)
         return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
-    if (params[0].mode == KRR_PCT_REF_INDEX && !cpu->gaps_are_nan) {
-        // compact REF_INDEX is P gathers per segment: nothing to fuse with
-        rc = krr_segmented_percentiles(ctx, cpu, params, n_params, cpu_value, cpu_count, cpu_flags, stream);
-        if (!rc) rc = krr_segmented_max(ctx, mem, mem_value, mem_count, mem_flags, stream);
-        return rc;
-    }
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-    hipStream_t st = (hipStream_t)stream;
-    int64_t Lmax = 0;
-    krr_multi_plan_info plan;
-    rc = prepare_multi(ctx, cpu, params, n_params, st, &Lmax, &plan);
+    return simple_run_multi_counts(ctx, cpu, mem, params, n_params, cpu_value, cpu_count, cpu_flags, mem_value,
+                                   mem_count, mem_flags, stream);
+}
+
+int krr_simple_run_pods_multi(krr_ctx* ctx, const krr_series* cpu_pods, const int64_t* pod_groups,
+                              const krr_series* mem, const krr_percentile_params* params, int32_t n_params,
+                              double* pod_value, int64_t* pod_count, uint32_t* pod_flags, double* cpu_value,
+                              int64_t* cpu_count, uint32_t* cpu_flags, int64_t* cpu_pod, double* mem_value,
+                              int64_t* mem_count, uint32_t* mem_flags, void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    if (!cpu_pods || !mem || !pod_groups) return set_err(ctx, KRR_E_INVALID, "null series or pod_groups%s", "");
+    int rc = check_series(ctx, cpu_pods);
+    if (!rc) rc = check_series(ctx, mem);
+    if (!rc) rc = check_params_multi(ctx, params, n_params);
     if (rc) return rc;
-    if (!plan.shared) {
-        // one percentile rides the fused launch with the memory half, the others are
-        // percentile-only passes: P + 1 half-passes instead of 2 P
-        rc = krr_simple_run(ctx, cpu, mem, &params[0], cpu_value, cpu_count, cpu_flags, mem_value, mem_count,
-                            mem_flags, stream);
-        for (int32_t j = 1; j < n_params && !rc; ++j)
-            rc = krr_segmented_percentile(ctx, cpu, &params[j], cpu_value + (int64_t)j * S, cpu_count,
-                                          cpu_flags + (int64_t)j * S, stream);
-        return rc;
-    }
-    const MultiArgs A = multi_args(cpu, params, n_params, Lmax, plan, cpu_value, cpu_count, cpu_flags);
-    return launch_multi(ctx, A, max_args(mem, mem_value, mem_count, mem_flags, nullptr), plan, st);
+    if (n_params == 1)
+        return krr_simple_run_pods(ctx, cpu_pods, pod_groups, mem, params, pod_value, pod_count, pod_flags, cpu_value,
+                                   cpu_count, cpu_flags, cpu_pod, mem_value, mem_count, mem_flags, nullptr, stream);
+    const int64_t n_pods = cpu_pods->n_segments, n_objects = mem->n_segments;
+    if (n_pods > 0 && (!pod_value || !pod_count || !pod_flags)) return set_err(ctx, KRR_E_INVALID, "null pod outputs%s", "");
+    if (n_objects > 0 && (!cpu_value || !cpu_count || !cpu_flags || !mem_value || !mem_count || !mem_flags))
+        return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+    rc = check_pod_span(ctx, pod_groups, n_objects, n_pods, stream);
+    if (rc) return rc;
+    if (n_objects == 0) return KRR_OK;
+    // the multi launch over n_pods CPU segments and n_objects memory segments, then one fold
+    // of all the rows on the same stream
+    rc = simple_run_multi_counts(ctx, cpu_pods, mem, params, n_params, pod_value, pod_count, pod_flags, mem_value,
+                                 mem_count, mem_flags, stream);
+    if (rc) return rc;
+    return krr_group_max(ctx, n_objects, pod_groups, n_params, n_pods, pod_value, pod_count, pod_flags, cpu_value,
+                         cpu_count, cpu_flags, cpu_pod, nullptr, stream);
 }
 
 }  // extern "C"

@@ -91,7 +91,7 @@ class SimpleStrategySettings(StrategySettings):
             return Decimal(1 + self.memory_buffer_percentage / 100)
 
     def aggregation(self) -> str:
-        # settings built by .construct() (simple_limit) carry no field: the default
+        # settings built by .construct() without the field: the default
         return CpuAggregation(getattr(self, "cpu_aggregation", CpuAggregation.CONCAT)).value
 
     def run_fleet(self, fleet: PackedFleet, device: Optional[int] = None) -> RawResults:

@@ -1,8 +1,10 @@
 """simple_limit on MI355X — ``simple`` with a CPU limit: the CPU request comes from one
 percentile and the CPU limit from a higher one, both from ONE fused kernel pass
 (krr_simple_run_multi: the candidate buffer kept for the request's percentile also holds
-the limit's).  Later upstream KRR ships a strategy of this name; the reference snapshot
-this package mirrors (KRR 1.0.0) does not, so the defaults below are this project's.
+the limit's).  ``cpu_aggregation`` "pods_max" takes both per pod and the max over the
+object's pods (krr_simple_run_pods_multi), as the later upstream strategy does.  Later
+upstream KRR ships a strategy of this name; the reference snapshot this package mirrors
+(KRR 1.0.0) does not, so the defaults below are this project's.
 
   CPU    request = value at ``cpu_request``, limit = value at ``cpu_limit``, each by the
          rule ``percentile_mode`` names (krr_amd.strategies.simple)
@@ -42,7 +44,7 @@ from krr_amd.core.abstract.strategies import (
 from krr_amd.core.engine import RawResults, default_engine, percentile_params
 from krr_amd.core.packing import PackedFleet, pack_resource
 from krr_amd.core.rounding import format_result, reference_context
-from krr_amd.strategies.simple import PercentileMode, SimpleStrategySettings
+from krr_amd.strategies.simple import CpuAggregation, PercentileMode, SimpleStrategySettings
 
 SHARDED_MESSAGE = ("simple_limit has no multi-GPU sharded path: the 32-byte result record holds one CPU value "
                    "(request and limit need two); run it on one GPU")
@@ -62,6 +64,11 @@ class SimpleLimitStrategySettings(StrategySettings):
         PercentileMode.SORTED_LOWER,
         description="CPU percentile rule: sorted_lower (default), linear (numpy), or ref_index (the reference's "
                     "positional pick: the limit may then fall below the request).",
+    )
+    cpu_aggregation: CpuAggregation = pd.Field(
+        CpuAggregation.CONCAT,
+        description="CPU over an object's pods: concat (one percentile over the pods' samples concatenated, "
+                    "reference KRR 1.0.0) or pods_max (the max over the pods of each pod's percentile).",
     )
     device: int = pd.Field(0, ge=0, description="HIP device that runs the kernels.")
 
@@ -85,7 +92,8 @@ class SimpleLimitStrategySettings(StrategySettings):
         cpu_from_raw / memory_from_raw turn raw kernel results into Decimals."""
         return SimpleStrategySettings.construct(
             cpu_percentile=self.cpu_request, memory_buffer_percentage=self.memory_buffer_percentage,
-            percentile_mode=PercentileMode(self.percentile_mode), device=self.device,
+            percentile_mode=PercentileMode(self.percentile_mode),
+            cpu_aggregation=CpuAggregation(self.cpu_aggregation), device=self.device,
             history_duration=self.history_duration, timeframe_duration=self.timeframe_duration)
 
     def memory_buffer(self) -> Decimal:
@@ -94,10 +102,25 @@ class SimpleLimitStrategySettings(StrategySettings):
 
     def run_fleet_multi(self, fleet: PackedFleet, device: Optional[int] = None) -> list:
         """One fused pass -> [RawResults at cpu_request, RawResults at cpu_limit] (they share
-        the memory arrays)."""
+        the memory arrays).  ``cpu_aggregation`` "pods_max": request and limit per pod, each the
+        max over the object's pods — its own first maximal pod — from one fused launch plus one
+        fold (krr_simple_run_pods_multi); the fleet's CPU series must carry pod boundaries (the
+        device packer writes none: ValueError).  NaN samples among the CPU values stay out of
+        contract, as in ``simple``: ``cpu_from_raw`` sees the folded flags and count."""
         params = self.params_list()
-        raws = default_engine(self.device if device is None else device).run_packed_multi(fleet, params)
-        if fleet.cpu.exact is not None or fleet.mem.exact is not None:
+        engine = default_engine(self.device if device is None else device)
+        exact = fleet.cpu.exact is not None or fleet.mem.exact is not None
+        agg = CpuAggregation(self.cpu_aggregation).value
+        if agg == CpuAggregation.PODS_MAX.value:
+            raws = engine.run_packed_multi(fleet, params, aggregation=agg, return_pods=exact)
+            if exact and fleet.n_objects:
+                from krr_amd.core.exact import resolve_pods
+
+                for raw, p in zip(raws, params):
+                    resolve_pods(fleet, raw, p)
+            return raws
+        raws = engine.run_packed_multi(fleet, params)
+        if exact:
             from krr_amd.core.exact import resolve
 
             for raw, p in zip(raws, params):
