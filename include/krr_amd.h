@@ -639,6 +639,26 @@ int krr_json_compact(krr_ctx* ctx, const krr_json_bodies* b, const double* scrat
                      const double* scratch_ts, const int64_t* counts, const int32_t* status,
                      const int64_t* out_pos, double* values, double* timestamps, void* stream);
 
+/* The pod boundaries of a parsed per-pod batch (cpu_aggregation = "pods_max" on device-packed
+ * fleets).  Body b is a pod segment iff status[b] == KRR_JSON_OK and counts[b] > 0 — what
+ * krr_pack_parse keeps.  Bodies are in fleet order: object o owns bodies body_groups[o] ..
+ * body_groups[o + 1] (device int64[n_objects + 1]).  One wave per object, on `stream`, in two
+ * launches around the caller's prefix sum:
+ *   pod_groups == NULL (and pod_offsets == NULL): pods_per_object[o] = the object's kept bodies,
+ *       longest_pod[o] = the samples of its longest kept body (0: none); either may be NULL;
+ *   pod_groups != NULL (device int64[n_objects + 1], the exclusive prefix sum of
+ *       pods_per_object): pod_offsets[pod_groups[o] + j] = out_pos[b] for the j-th kept body b
+ *       of object o, and pod_offsets[pod_groups[n_objects]] = the CSR's size; pod_offsets holds
+ *       n_bodies + 1 words, of which the first pod_groups[n_objects] + 1 are written.
+ *       pods_per_object / longest_pod are written as well when given.
+ * out_pos is krr_json_compact's.  Indices outside the arrays (a table that does not describe
+ * the batch) are not followed.  KRR_E_INVALID: a null buffer, negative sizes, pod_groups
+ * without pod_offsets or the reverse, no output at all; nothing is launched then. */
+int krr_json_pod_bounds(krr_ctx* ctx, int64_t n_objects, const int64_t* body_groups, int64_t n_bodies,
+                        const int64_t* counts, const int32_t* status, const int64_t* out_pos,
+                        const int64_t* pod_groups, int64_t* pods_per_object, int64_t* longest_pod,
+                        int64_t* pod_offsets, void* stream);
+
 /* n host -> device copies enqueued on `stream` in order (dst[i] <- src[i], bytes[i] bytes;
  * src page-locked for an asynchronous copy): the device packer's staged runs and body
  * offsets, one call per chunk instead of one runtime call per run from Python. */

@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "krr_abi_version",
     "krr_json_parse",
     "krr_json_compact",
+    "krr_json_pod_bounds",
     "krr_copy_h2d_batch",
     "krr_json_find_series",
     "krr_json_parse_segments",
@@ -383,6 +384,8 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_json_parse.restype = ctypes.c_int
         lib.krr_json_compact.argtypes = [vp, jb, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_json_compact.restype = ctypes.c_int
+        lib.krr_json_pod_bounds.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_json_pod_bounds.restype = ctypes.c_int
         lib.krr_copy_h2d_batch.argtypes = [vp, i64, vp, vp, vp, vp]
         lib.krr_copy_h2d_batch.restype = ctypes.c_int
         lib.krr_json_find_series.argtypes = [vp, jb, i64, i64, i64, vp, i64, vp, vp]
@@ -944,6 +947,33 @@ class Context:
             scratch_ts.data_ptr() if timestamps is not None else None, counts.data_ptr(), status.data_ptr(),
             out_pos.data_ptr(), values.data_ptr(), timestamps.data_ptr() if timestamps is not None else None,
             self._stream(stream)))
+
+    def json_pod_bounds(self, body_groups, counts, status, out_pos, pod_groups=None, pods_per_object=None,
+                        longest_pod=None, pod_offsets=None, stream=None) -> None:
+        """The pod boundaries of a parsed per-pod batch (krr_json_pod_bounds): body_groups int64
+        [n_objects + 1] (object o owns bodies body_groups[o] .. body_groups[o + 1]); counts /
+        status / out_pos as json_compact's.  Without ``pod_groups``: pods_per_object and
+        longest_pod (int64 [n_objects]).  With it (int64 [n_objects + 1], their exclusive prefix
+        sum): pod_offsets (int64 [n_bodies + 1], the first n_pods + 1 written)."""
+        _check_tensor(body_groups, "int64", 1)
+        S, n = body_groups.numel() - 1, counts.numel()
+        _check_tensor(counts, "int64")
+        _check_tensor(status, "int32", n)
+        _check_tensor(out_pos, "int64", n)
+        for t in (pods_per_object, longest_pod):
+            if t is not None:
+                _check_tensor(t, "int64", S)
+        if pod_groups is not None:
+            _check_tensor(pod_groups, "int64", S + 1)
+        if pod_offsets is not None:
+            _check_tensor(pod_offsets, "int64", n + 1)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        self._check(self._lib.krr_json_pod_bounds(
+            self._h, S, body_groups.data_ptr(), n, counts.data_ptr(), status.data_ptr(), out_pos.data_ptr(),
+            ptr(pod_groups), ptr(pods_per_object), ptr(longest_pod), ptr(pod_offsets), self._stream(stream)))
 
     def copy_h2d_batch(self, dst, src, nbytes, stream=None) -> None:
         """int64 arrays (numpy) of device destinations, host sources (page-locked) and byte

@@ -13,7 +13,10 @@ Here the raw bodies cross PCIe instead and the MI355X parses them (include/krr_a
      per body, the values array by all 64 lanes, values to a scratch slot per body;
   3. one synchronisation reads the bodies' statuses and the CSR size; the counts' prefix
      sums (bodies are in fleet order) give the segment offsets and each body's place, and
-     ``krr_json_compact`` writes the CSR.
+     ``krr_json_compact`` writes the CSR.  The same counts give the pod boundaries
+     (``PackedSeries.pod_offsets`` / ``pod_groups`` / ``pod_max_len``, cpu_aggregation =
+     "pods_max"): ``krr_json_pod_bounds``, one wave per object, before that one
+     synchronisation, whose transfer also carries the number of pods.
 
 A body outside the form the device decides (KRR_JSON_HOST: escapes in keys or values,
 whitespace inside a value string, other NaN/Inf spellings, > 19 significant digits, an error
@@ -32,7 +35,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from krr_amd import _native
-from krr_amd.core.packing import PackedSeries
+from krr_amd.core.packing import PackedSeries, pod_fields
 from krr_amd.core.prom_native import KRR_PACK_OK, PrometheusResponseError, load_library, pack_query_range_bodies
 
 
@@ -787,10 +790,19 @@ class DevicePacker:
             offsets = np.zeros(n_obj + 1, dtype=np.int64)
             np.cumsum(seg, out=offsets[1:])
             n_vals = int(offsets[-1])
-            # the gather's three columns and the offsets in ONE page-locked buffer, one copy
-            cols = torch.empty(3 * ns + n_obj + 1, dtype=torch.int64, pin_memory=True)
+            # the pod boundaries: a slot that kept samples is a pod segment (slots are in object
+            # order, then K8sObjectData.pods order)
+            is_pod = kept > 0
+            pod_offsets, pod_groups = pod_fields(kept[is_pod], np.bincount(plan.slot_obj[is_pod], minlength=n_obj)
+                                                 if ns else np.zeros(n_obj, dtype=np.int64))
+            n_pods = pod_offsets.size - 1
+            # the gather's three columns, the offsets and the pod boundaries in ONE page-locked
+            # buffer, one copy
+            o_end = 3 * ns + n_obj + 1
+            cols = torch.empty(o_end + n_pods + 1 + n_obj + 1, dtype=torch.int64, pin_memory=True)
             cn = cols.numpy()
-            cn[:ns], cn[ns:2 * ns], cn[2 * ns:3 * ns], cn[3 * ns:] = np.maximum(slot_src, 0), kept, dst, offsets
+            cn[:ns], cn[ns:2 * ns], cn[2 * ns:3 * ns] = np.maximum(slot_src, 0), kept, dst
+            cn[3 * ns:o_end], cn[o_end:o_end + n_pods + 1], cn[o_end + n_pods + 1:] = offsets, pod_offsets, pod_groups
             with torch.cuda.stream(st):
                 values = torch.empty(max(n_vals, 1), dtype=torch.float64, device=dev)
                 ts = torch.empty(max(n_vals, 1), dtype=torch.float64, device=dev) if want_ts else None
@@ -798,8 +810,10 @@ class DevicePacker:
                 if ns:
                     self.ctx.json_gather(cols_d[:ns], cols_d[ns:2 * ns], cols_d[2 * ns:3 * ns], tmp_v, tmp_t, values,
                                          ts, stream=st)
-                offs_d = cols_d[3 * ns:]
-            series = PackedSeries(values[:n_vals], offs_d, int(seg.max()) if n_obj else 0)
+                offs_d = cols_d[3 * ns:o_end]
+            series = PackedSeries(values[:n_vals], offs_d, int(seg.max()) if n_obj else 0,
+                                  pod_offsets=cols_d[o_end:o_end + n_pods + 1], pod_groups=cols_d[o_end + n_pods + 1:],
+                                  pod_max_len=int(kept.max(initial=0)))
             out.append(DevicePacked(series, "device", 0, slot_cnt if want_counts else None,
                                     ts[:n_vals] if ts is not None else None))
         clock.append(time.perf_counter())
@@ -853,7 +867,9 @@ class DevicePacker:
             out = []
             for per_object_bodies in resources:
                 offs = torch.zeros(len(per_object_bodies) + 1, dtype=torch.int64, device=dev)
-                out.append(DevicePacked(PackedSeries(torch.empty(0, dtype=torch.float64, device=dev), offs, 0),
+                out.append(DevicePacked(PackedSeries(torch.empty(0, dtype=torch.float64, device=dev), offs, 0,
+                                                     pod_offsets=torch.zeros(1, dtype=torch.int64, device=dev),
+                                                     pod_groups=torch.zeros_like(offs), pod_max_len=0),
                                         "device", 0,
                                         torch.empty(0, dtype=torch.int64, device=dev) if want_counts else None,
                                         torch.empty(0, dtype=torch.float64, device=dev) if want_ts else None))
@@ -867,24 +883,44 @@ class DevicePacker:
         lens, boffs, total, jb, tmp_v, tmp_t = self._upload(flat, want_ts, st, launch, strip=self.strip)
         R = len(resources)
         with torch.cuda.stream(st):
-            obj_t = torch.from_numpy(np.asarray(obj, dtype=np.int64)).to(dev, non_blocking=False)
+            # each body's object and each object's first body (bodies are in fleet order), one copy
+            obj_np = np.asarray(obj, dtype=np.int64)
+            table = np.concatenate([obj_np, np.searchsorted(obj_np, np.arange(n_obj + 1), side="left")])
+            table_t = torch.from_numpy(table.astype(np.int64, copy=False)).to(dev, non_blocking=False)
+            obj_t, body_groups = table_t[:nb], table_t[nb:]
             seg = torch.zeros(n_obj, dtype=torch.int64, device=dev).index_add_(0, obj_t, counts)
             offsets = torch.zeros(n_obj + 1, dtype=torch.int64, device=dev)
             torch.cumsum(seg, 0, out=offsets[1:])
+            out_pos = torch.cumsum(counts, 0) - counts
+            # the pod boundaries (krr_json_pod_bounds): the kept bodies per object and each
+            # object's longest, their prefix sum, then every kept body's place in the CSR
+            pods = torch.empty(n_obj, dtype=torch.int64, device=dev)
+            longest = torch.empty(n_obj, dtype=torch.int64, device=dev)
+            self.ctx.json_pod_bounds(body_groups, counts, status, out_pos, pods_per_object=pods,
+                                     longest_pod=longest, stream=st)
+            pod_groups = torch.zeros(n_obj + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(pods, 0, out=pod_groups[1:])
+            pod_offsets = torch.empty(nb + 1, dtype=torch.int64, device=dev)  # n_pods + 1 of them written
+            self.ctx.json_pod_bounds(body_groups, counts, status, out_pos, pod_groups=pod_groups,
+                                     pod_offsets=pod_offsets, stream=st)
             host_flag = (status == _native.KRR_JSON_HOST).to(torch.int64)
+            zero = offsets[0]
+            # per resource: bodies left to the host, longest segment, first pod, longest pod, first value
             per_res = [torch.stack([host_flag[body0[r]:body0[r + 1]].sum(),
-                                    seg[obj0[r]:obj0[r + 1]].max() if obj0[r + 1] > obj0[r] else offsets[0]])
+                                    seg[obj0[r]:obj0[r + 1]].max() if obj0[r + 1] > obj0[r] else zero,
+                                    pod_groups[obj0[r]],
+                                    longest[obj0[r]:obj0[r + 1]].max() if obj0[r + 1] > obj0[r] else zero,
+                                    offsets[obj0[r]]])
                        for r in range(R)]
-            summary = torch.stack(per_res + [torch.stack([offsets[-1], offsets[-1]])]).cpu()  # the one sync
+            end = torch.stack([offsets[-1], offsets[-1], pod_groups[-1], zero, offsets[-1]])
+            summary = torch.stack(per_res + [end]).cpu()  # the one sync
         n_vals = int(summary[R, 0])
         with torch.cuda.stream(st):
-            out_pos = torch.cumsum(counts, 0) - counts
             values = torch.empty(max(n_vals, 1), dtype=torch.float64, device=dev)
             ts = torch.empty(max(n_vals, 1), dtype=torch.float64, device=dev) if want_ts else None
             self.ctx.json_compact(jb, tmp_v, tmp_t, counts, status, out_pos, values, ts, stream=st)
             pc = torch.where(status == _native.KRR_JSON_DROPPED, torch.full_like(counts, -1), counts) \
                 if want_counts else None
-        offs_h = None
         out = []
         for r in range(R):
             n_host, max_len = int(summary[r, 0]), int(summary[r, 1])
@@ -897,12 +933,15 @@ class DevicePacker:
                 c_r = rest.pop(0) if want_counts else None
                 out.append(DevicePacked(res[0], "host", n_host, c_r, t_r))
                 continue
-            if offs_h is None:
-                offs_h = offsets.cpu()
-            lo, hi = int(offs_h[obj0[r]]), int(offs_h[obj0[r + 1]])
+            # the resource's range of values and of pod segments, both rebased to start at 0
+            lo, hi = int(summary[r, 4]), int(summary[r + 1, 4])
+            g_lo, g_hi = int(summary[r, 2]), int(summary[r + 1, 2])
             o_r = offsets[obj0[r]:obj0[r + 1] + 1] - lo
-            out.append(DevicePacked(PackedSeries(values[lo:hi], o_r, max_len if obj0[r + 1] > obj0[r] else 0),
-                                    "device", 0, pc[body0[r]:body0[r + 1]] if want_counts else None,
+            series = PackedSeries(values[lo:hi], o_r, max_len if obj0[r + 1] > obj0[r] else 0,
+                                  pod_offsets=pod_offsets[g_lo:g_hi + 1] - lo,
+                                  pod_groups=pod_groups[obj0[r]:obj0[r + 1] + 1] - g_lo,
+                                  pod_max_len=int(summary[r, 3]))
+            out.append(DevicePacked(series, "device", 0, pc[body0[r]:body0[r + 1]] if want_counts else None,
                                     ts[lo:hi] if ts is not None else None))
         # the staging buffer is reused by the next call: its copies are done (the parse
         # launches waited for them before the summary synchronised)

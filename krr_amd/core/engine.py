@@ -236,10 +236,7 @@ class SimpleEngine:
             pods.update({"pod_value": [], "pod_count": [], "pod_flags": [], "cpu_pod": [], "locate": pod_loc})
         pod_lo = 0
         for lo, hi, part, cs, ms in self._chunks(fleet):
-            view = pod_view(part.cpu)
-            po = torch.from_numpy(np.ascontiguousarray(view.offsets)).to(dev)
-            pg = torch.from_numpy(np.ascontiguousarray(part.cpu.pod_groups, dtype=np.int64)).to(dev)
-            pcs = ctx.series(cs._keep[0], po, max(view.max_len, 1), view.gaps_are_nan)
+            view, pg, pcs = self._pod_series(ctx, part, cs)
             n = view.n_segments
             chunk_out = {k: v[lo:hi] for k, v in out.items()}
             chunk_out.update(pod_value=torch.empty(n, dtype=torch.float64, device=dev),
@@ -258,6 +255,32 @@ class SimpleEngine:
                                        pcs, ms, params, pod_out, pod_loc, pod_lo, names=("cpu",))
             pod_lo += n
         return loc
+
+    def _pod_series(self, ctx, part: PackedFleet, cs):
+        """A chunk's CPU values as one segment per pod: (the pod view, pod_groups in HBM, the
+        krr_series over the pod segments).  Host-packed series go through ``pod_view`` and an
+        upload of the two arrays; a fleet resident in HBM (device packer: one chunk, canonical)
+        hands its pod offsets and groups tensors to the kernels as they are."""
+        import torch
+
+        from krr_amd.core.packing import PackedSeries, pod_view
+
+        dev = torch.device("cuda", self.device)
+        cpu = part.cpu
+        po, pg = cpu.pod_offsets, cpu.pod_groups
+        if all(isinstance(t, torch.Tensor) and t.is_cuda for t in (cpu.values, po, pg)):
+            if po.device != dev or pg.device != dev:
+                raise ValueError(f"pod boundaries on {po.device}, engine runs on {dev}: pack on the engine's device")
+            po, pg = po.contiguous(), pg.contiguous()
+            longest = cpu.pod_max_len
+            if longest is None:  # a resident series put together without it: one synchronising read
+                longest = int((po[1:] - po[:-1]).max()) if po.numel() > 1 else 0
+            view = PackedSeries(cpu.values, po, int(longest), cpu.gaps_are_nan)
+        else:
+            view = pod_view(cpu)
+            po = torch.from_numpy(np.ascontiguousarray(view.offsets)).to(dev)
+            pg = torch.from_numpy(np.ascontiguousarray(cpu.pod_groups, dtype=np.int64)).to(dev)
+        return view, pg, ctx.series(cs._keep[0], po, max(view.max_len, 1), view.gaps_are_nan)
 
     def _chunks(self, fleet: PackedFleet):
         """Per chunk of ``_chunk_bounds``: (lo, hi, the chunk's fleet, its CPU series, its memory
@@ -374,10 +397,7 @@ class SimpleEngine:
             pod_chunks = {k: [] for k, _, _ in pod_keys}
             pod_lo = 0
             for lo, hi, part, cs, ms in self._chunks(fleet):
-                view = pod_view(part.cpu)
-                po = torch.from_numpy(np.ascontiguousarray(view.offsets)).to(dev)
-                pg = torch.from_numpy(np.ascontiguousarray(part.cpu.pod_groups, dtype=np.int64)).to(dev)
-                pcs = ctx.series(cs._keep[0], po, max(view.max_len, 1), view.gaps_are_nan)
+                view, pg, pcs = self._pod_series(ctx, part, cs)
                 n = view.n_segments
                 whole = hi - lo == S
                 # a chunk's rows are not contiguous in the [P, S] outputs: its own [P, n] block

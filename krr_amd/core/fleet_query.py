@@ -39,7 +39,7 @@ from typing import Callable, Sequence
 import numpy as np
 
 from krr_amd.core.models.allocations import ResourceType
-from krr_amd.core.packing import PackedFleet, PackedSeries
+from krr_amd.core.packing import PackedFleet, PackedSeries, pod_fields
 from krr_amd.core.prom_native import KRR_PACK_OK, PrometheusResponseError, _ptr, load_library
 
 # The reference's selectors (prometheus.py:123 and :137), without the pod/ns/container matchers.
@@ -195,7 +195,8 @@ class FleetQueryPlan:
         """bodies[g] = the raw query_range response body of ``queries(resource)[g]``.
 
         Returns a PackedSeries (segment o = object o's pods with data, concatenated
-        in K8sObjectData.pods order), plus the timestamps if ``want_timestamps`` and
+        in K8sObjectData.pods order, with the pod boundaries ``pod_offsets`` / ``pod_groups``
+        the per-pod packer gives for the same samples), plus the timestamps if ``want_timestamps`` and
         the per-(object, pod) sample counts (-1: dropped) if ``return_pod_counts``.
         ``alloc(n)``: optional allocator of the float64 value array (pinned memory).
         """
@@ -221,20 +222,27 @@ class FleetQueryPlan:
             values = alloc(n) if alloc is not None else np.empty(n, dtype=np.float64)
             offsets = np.empty(no + 1, dtype=np.int64)
             ts = np.empty(n, dtype=np.float64) if want_timestamps else None
-            counts = np.empty(max(ns, 1), dtype=np.int64) if return_pod_counts else None
+            counts = np.empty(max(ns, 1), dtype=np.int64)
             rc = lib.krr_pack_copy(h, _ptr(values), _ptr(offsets), _ptr(ts) if ts is not None else None,
-                                   _ptr(counts) if counts is not None else None, int(threads))
+                                   _ptr(counts), int(threads))
             if rc != KRR_PACK_OK:
                 raise PrometheusResponseError(rc, "krr_pack_copy failed")
             max_len = int(lib.krr_pack_max_len(h))
         finally:
             if h:
                 lib.krr_pack_free(h)
-        out: list = [PackedSeries(values, offsets, max_len)]
+        series = PackedSeries(values, offsets, max_len)
+        # the pod boundaries: a slot that kept samples is a pod segment (slots are in object
+        # order, then K8sObjectData.pods order), as the per-pod packer's kept bodies are
+        counts = counts[:ns]
+        keep = counts > 0
+        series.pod_offsets, series.pod_groups = pod_fields(
+            counts[keep], np.bincount(self.slot_obj[keep], minlength=no) if ns else np.zeros(no, dtype=np.int64))
+        out: list = [series]
         if want_timestamps:
             out.append(ts)
         if return_pod_counts:
-            out.append(counts[:ns])
+            out.append(counts)
         return out[0] if len(out) == 1 else tuple(out)
 
     def group_sorted_slots(self):

@@ -42,9 +42,14 @@ class PackedSeries:
     # The pod boundaries inside the segments (CPU series; cpu_aggregation = "pods_max"): pod
     # segment j is values[pod_offsets[j]:pod_offsets[j + 1]] (int64 [n_pods + 1]) and object
     # s owns the pod segments pod_groups[s] .. pod_groups[s + 1] (int64 [S + 1]), so that
-    # pod_offsets[pod_groups[s]] == offsets[s].  None: the packer kept no pod boundaries.
+    # pod_offsets[pod_groups[s]] == offsets[s].  Every packer attaches them — numpy arrays, or
+    # int64 tensors in HBM beside the values (device packer); None: a series built by hand
+    # without them.
     pod_offsets: Optional[np.ndarray] = None
     pod_groups: Optional[np.ndarray] = None
+    # the longest pod segment, where the packer knows it (series in HBM: np.diff(pod_offsets).max()
+    # on the host would synchronise); None: taken from pod_offsets when needed
+    pod_max_len: Optional[int] = None
 
     @property
     def n_pods(self) -> int:
@@ -83,13 +88,15 @@ def pod_fields(pod_lens, pods_per_object) -> tuple[np.ndarray, np.ndarray]:
 def pod_view(ps: PackedSeries) -> PackedSeries:
     """The same values as ONE SEGMENT PER POD (cpu_aggregation = "pods_max"): offsets are the
     pod offsets; a pod takes its object's exactness class (an upper bound of its own) and its
-    own sample list as ``sources``.  Raises ValueError for a series packed without pod
-    boundaries (the device packer, krr_amd.core.device_pack, keeps none)."""
+    own sample list as ``sources``.  Host-packed series (numpy fields); a series in HBM goes to
+    the kernels with its tensors as they are (krr_amd.core.engine).  Raises ValueError for a
+    series without pod boundaries (one built by hand: every packer attaches them)."""
     if ps.pod_offsets is None or ps.pod_groups is None:
         raise ValueError("cpu_aggregation='pods_max' needs the pod boundaries (PackedSeries.pod_offsets / "
-                         "pod_groups), which this series was packed without: the device packer "
-                         "(krr_amd.core.device_pack.DevicePacker) keeps none; pack on the host (pack_histories, "
-                         "pack_prometheus, pack_dense_grid, pack_query_range_bodies)")
+                         "pod_groups), which this series does not carry: every packer attaches them "
+                         "(pack_histories, pack_prometheus, pack_dense_grid, pack_query_range_bodies, "
+                         "FleetQueryPlan.pack and the device packer, krr_amd.core.device_pack.DevicePacker); a "
+                         "PackedSeries built by hand must set them")
     pod_offsets = np.asarray(ps.pod_offsets, dtype=np.int64)
     per_object = np.diff(np.asarray(ps.pod_groups, dtype=np.int64))
     exact = sources = None

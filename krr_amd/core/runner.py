@@ -552,22 +552,42 @@ def _concat_raw(raws):
 
 
 def _concat_fleets(parts, device):
-    """PackedFleets of consecutive object ranges (HBM and/or host) -> one PackedFleet in HBM."""
+    """PackedFleets of consecutive object ranges (HBM and/or host) -> one PackedFleet in HBM,
+    with the parts' pod boundaries (when every part carries them)."""
+    import numpy as np
     import torch
 
     from krr_amd.core.packing import PackedFleet, PackedSeries
 
     dev = torch.device("cuda", int(device))
 
+    def tensor(a):
+        return a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64))
+
     def cat(series):
-        vals, offs, base = [], [torch.zeros(1, dtype=torch.int64, device=dev)], 0
+        zero = torch.zeros(1, dtype=torch.int64, device=dev)
+        pods = all(ps.pod_offsets is not None and ps.pod_groups is not None for ps in series)
+        vals, offs, base = [], [zero], 0
+        pod_offs, pod_groups, pod_base, pod_max = [zero], [zero], 0, 0
         for ps in series:
             v = ps.values if isinstance(ps.values, torch.Tensor) else torch.from_numpy(ps.values)
             o = ps.offsets if isinstance(ps.offsets, torch.Tensor) else torch.from_numpy(ps.offsets)
             vals.append(v.to(dev))
             offs.append(o[1:].to(dev) + base)
+            if pods:  # the part's pod segments after those before it, its samples after theirs
+                po, pg = tensor(ps.pod_offsets), tensor(ps.pod_groups)
+                pod_offs.append(po[1:].to(dev) + base)
+                pod_groups.append(pg[1:].to(dev) + pod_base)
+                pod_base += ps.n_pods
+                longest = ps.pod_max_len
+                if longest is None:
+                    longest = int((po[1:] - po[:-1]).max()) if ps.n_pods else 0
+                pod_max = max(pod_max, int(longest))
             base += int(o[-1])
-        return PackedSeries(torch.cat(vals), torch.cat(offs), max(int(ps.max_len) for ps in series))
+        out = PackedSeries(torch.cat(vals), torch.cat(offs), max(int(ps.max_len) for ps in series))
+        if pods:
+            out.pod_offsets, out.pod_groups, out.pod_max_len = torch.cat(pod_offs), torch.cat(pod_groups), pod_max
+        return out
 
     return PackedFleet(cat([p.cpu for p in parts]), cat([p.mem for p in parts]))
 

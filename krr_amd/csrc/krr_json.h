@@ -260,6 +260,61 @@ __global__ __launch_bounds__(256) void k_json_compact(CompactArgs C) {
     }
 }
 
+struct PodBoundsArgs {
+    const int64_t* body_groups;  // [n_objects + 1]: object o owns bodies body_groups[o] .. body_groups[o + 1]
+    const int64_t* counts;
+    const int32_t* status;
+    const int64_t* out_pos;      // exclusive prefix of counts
+    const int64_t* pod_groups;   // [n_objects + 1] exclusive prefix of the kept bodies per object, or null
+    int64_t* pods;               // [n_objects] kept bodies per object, or null
+    int64_t* longest;            // [n_objects] longest kept body per object, or null
+    int64_t* pod_offsets;        // [n_bodies + 1] (given with pod_groups), or null
+    int64_t n_objects, n_bodies;
+};
+
+// The pod boundaries of a parsed per-pod batch: a body is a pod segment iff it is JSON_OK and
+// holds samples (what the host packer keeps).  One wave per object, its bodies 64 at a time:
+// one scan of the keep flags per block on top of the kept bodies of the blocks before gives
+// each kept body its place among the object's pods.  Without pod_groups the wave only counts
+// (the caller's prefix sum over `pods` is pod_groups of the second launch).  Every index is
+// held inside the arrays' sizes, whatever body_groups / pod_groups hold.
+__global__ __launch_bounds__(64) void k_json_pod_bounds(PodBoundsArgs P) {
+    const int lane = threadIdx.x;
+    for (int64_t o = blockIdx.x; o < P.n_objects; o += gridDim.x) {
+        int64_t b0 = P.body_groups[o], b1 = P.body_groups[o + 1];
+        b0 = b0 < 0 ? 0 : (b0 > P.n_bodies ? P.n_bodies : b0);
+        b1 = b1 < b0 ? b0 : (b1 > P.n_bodies ? P.n_bodies : b1);
+        const int64_t first = P.pod_offsets ? P.pod_groups[o] : 0;
+        int64_t base = 0;      // kept bodies of the blocks before
+        uint64_t longest = 0;
+        for (int64_t blk = b0; blk < b1; blk += kWave) {
+            const int64_t b = blk + lane;
+            int64_t n = 0;
+            if (b < b1 && P.status[b] == JSON_OK) n = P.counts[b];
+            const uint32_t keep = n > 0 ? 1u : 0u;
+            const uint32_t incl = wave_scan32(keep, 0u, OpAdd32{});
+            if (keep) {
+                if ((uint64_t)n > longest) longest = (uint64_t)n;
+                const int64_t j = first + base + (int64_t)incl - 1;
+                if (P.pod_offsets && j >= 0 && j < P.n_bodies) P.pod_offsets[j] = P.out_pos[b];
+            }
+            base += (int64_t)lane_bcast32(incl, kWave - 1);
+        }
+        longest = wave_max_u64(longest);
+        if (lane == 0) {
+            if (P.pods) P.pods[o] = base;
+            if (P.longest) P.longest[o] = (int64_t)longest;
+        }
+    }
+    if (blockIdx.x == 0 && lane == 0 && P.pod_offsets) {  // pod_offsets[n_pods] = the CSR's size
+        int64_t n_pods = P.pod_groups[P.n_objects];
+        n_pods = n_pods < 0 ? 0 : (n_pods > P.n_bodies ? P.n_bodies : n_pods);
+        const int64_t last = P.n_bodies - 1;
+        P.pod_offsets[n_pods] =
+            last < 0 ? 0 : P.out_pos[last] + (P.status[last] == JSON_OK ? P.counts[last] : 0);
+    }
+}
+
 
 // ---- grouped bodies ("sum by (pod) (...)"): one wave per SERIES ----
 // A grouped body holds one series per pod (megabytes per body, a few bodies per fleet), so

@@ -4769,6 +4769,30 @@ int krr_json_compact(krr_ctx* ctx, const krr_json_bodies* b, const double* scrat
     return KRR_OK;
 }
 
+int krr_json_pod_bounds(krr_ctx* ctx, int64_t n_objects, const int64_t* body_groups, int64_t n_bodies,
+                        const int64_t* counts, const int32_t* status, const int64_t* out_pos,
+                        const int64_t* pod_groups, int64_t* pods_per_object, int64_t* longest_pod,
+                        int64_t* pod_offsets, void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    if (n_objects < 0 || n_bodies < 0) return set_err(ctx, KRR_E_INVALID, "json: negative object or body count%s", "");
+    if ((pod_groups == nullptr) != (pod_offsets == nullptr))
+        return set_err(ctx, KRR_E_INVALID, "json: pod_groups and pod_offsets go together%s", "");
+    if (!pod_offsets && !pods_per_object && !longest_pod)
+        return set_err(ctx, KRR_E_INVALID, "json: no output buffer%s", "");
+    if (!body_groups || (n_bodies > 0 && (!counts || !status || !out_pos)))
+        return set_err(ctx, KRR_E_INVALID, "json: null buffer%s", "");
+    if (n_objects == 0 && !pod_offsets) return KRR_OK;
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    json::PodBoundsArgs P{body_groups, counts, status, out_pos, pod_groups, pods_per_object, longest_pod,
+                          pod_offsets, n_objects, n_bodies};
+    // (a batch without objects still writes pod_offsets[0])
+    hipLaunchKernelGGL(json::k_json_pod_bounds, dim3(grid_for(n_objects > 0 ? n_objects : 1)), dim3(64), 0,
+                       (hipStream_t)stream, P);
+    KRR_HIP(ctx, hipGetLastError());
+    return KRR_OK;
+}
+
 int krr_copy_h2d_batch(krr_ctx* ctx, int64_t n, void* const* dst, const void* const* src, const int64_t* bytes,
                        void* stream) {
     if (!ctx) return KRR_E_INVALID;

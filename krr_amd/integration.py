@@ -230,17 +230,25 @@ async def fetch_grouped_fleet(runner: Any, objects: Sequence[Any], settings, par
 
 def _reorder(series: list, order: list, alloc=None):
     """Concatenate PackedSeries whose segments are objects ``order`` and permute the segments
-    into object order 0..n-1 (numpy on the host, or torch for series already in HBM)."""
+    into object order 0..n-1 (numpy on the host, or torch for series already in HBM).  The pod
+    boundaries travel with the objects — each keeps its own pods in their order — when every
+    part carries them; otherwise the result has none."""
     from krr_amd.core.packing import PackedSeries
 
+    pods = bool(series) and all(s.pod_offsets is not None and s.pod_groups is not None for s in series)
     on_dev = [s for s in series if not isinstance(s.values, np.ndarray)]
     if on_dev:  # device packer output (torch, HBM) — one cluster's batch may have gone to the host packer
         import torch
 
         dev = on_dev[0].values.device
+
+        def to_dev(a):
+            return None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.int64)).to(dev)
+
         series = [s if not isinstance(s.values, np.ndarray) else
                   PackedSeries(torch.from_numpy(np.ascontiguousarray(s.values, np.float64)).to(dev),
-                               torch.from_numpy(np.ascontiguousarray(s.offsets, np.int64)).to(dev), s.max_len)
+                               to_dev(s.offsets), s.max_len, pod_offsets=to_dev(s.pod_offsets),
+                               pod_groups=to_dev(s.pod_groups))
                   for s in series]
         lens = torch.cat([s.offsets[1:] - s.offsets[:-1] for s in series])
         bases = torch.tensor(np.cumsum([0] + [int(s.values.numel()) for s in series])[:-1], device=dev)
@@ -254,7 +262,22 @@ def _reorder(series: list, order: list, alloc=None):
         total = int(offsets[-1].item())
         seg = torch.repeat_interleave(torch.arange(len(order), device=dev), lens_o)
         pos = torch.arange(total, device=dev) - offsets[:-1][seg] + srcs_o[seg]
-        return PackedSeries(flat[pos], offsets, max(s.max_len for s in series))
+        out = PackedSeries(flat[pos], offsets, max(s.max_len for s in series))
+        if pods:
+            # per object of the concatenation: its pods and where they start among the parts' pods
+            per_obj = torch.cat([s.pod_groups[1:] - s.pod_groups[:-1] for s in series])[inv]
+            pod_bases = torch.tensor(np.cumsum([0] + [s.n_pods for s in series])[:-1], device=dev)
+            first = torch.cat([s.pod_groups[:-1] + b for s, b in zip(series, pod_bases)])[inv]
+            pod_lens = torch.cat([s.pod_offsets[1:] - s.pod_offsets[:-1] for s in series])
+            groups = torch.zeros(len(order) + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(per_obj, 0, out=groups[1:])
+            owner = torch.repeat_interleave(torch.arange(len(order), device=dev), per_obj)
+            lens_p = pod_lens[torch.arange(owner.numel(), device=dev) - groups[:-1][owner] + first[owner]]
+            pod_offsets = torch.zeros(owner.numel() + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(lens_p, 0, out=pod_offsets[1:])
+            out.pod_offsets, out.pod_groups = pod_offsets, groups
+            out.pod_max_len = int(lens_p.max().item()) if lens_p.numel() else 0
+        return out
     lens = np.concatenate([np.diff(s.offsets) for s in series]) if series else np.zeros(0, np.int64)
     srcs = np.concatenate([s.offsets[:-1] + base for s, base in
                            zip(series, np.cumsum([0] + [s.values.size for s in series])[:-1])]) \
@@ -268,7 +291,21 @@ def _reorder(series: list, order: list, alloc=None):
     values = alloc(int(offsets[-1])) if alloc is not None else np.empty(int(offsets[-1]), dtype=np.float64)
     for j in range(len(order)):
         values[offsets[j]:offsets[j + 1]] = flat[srcs_o[j]:srcs_o[j] + lens_o[j]]
-    return PackedSeries(values, offsets, int(lens.max(initial=0)))
+    out = PackedSeries(values, offsets, int(lens.max(initial=0)))
+    if pods:
+        # per object of the concatenation: its pods and where they start among the parts' pods
+        per_obj = np.concatenate([np.diff(np.asarray(s.pod_groups, np.int64)) for s in series])[inv]
+        pod_bases = np.cumsum([0] + [s.n_pods for s in series])[:-1]
+        first = np.concatenate([np.asarray(s.pod_groups, np.int64)[:-1] + b for s, b in zip(series, pod_bases)])[inv]
+        pod_lens = np.concatenate([np.diff(np.asarray(s.pod_offsets, np.int64)) for s in series])
+        groups = np.zeros(len(order) + 1, dtype=np.int64)
+        np.cumsum(per_obj, out=groups[1:])
+        owner = np.repeat(np.arange(len(order), dtype=np.int64), per_obj)
+        lens_p = pod_lens[np.arange(owner.size, dtype=np.int64) - groups[:-1][owner] + first[owner]]
+        pod_offsets = np.zeros(owner.size + 1, dtype=np.int64)
+        np.cumsum(lens_p, out=pod_offsets[1:])
+        out.pod_offsets, out.pod_groups, out.pod_max_len = pod_offsets, groups, int(lens_p.max(initial=0))
+    return out
 
 
 # ---- Runner._collect_result with the fleet-vectorised scan ------------------------------------
@@ -312,9 +349,9 @@ def install(runner_cls: Any = None, *, loader: str = "reference", scan: str = "r
     host packer, "hybrid" both at once on disjoint object ranges
     (``BatchedRunner.pack_hybrid``; loader="grouped" parses as "device").
     ``cpu_aggregation="pods_max"``: CPU is the max over an object's pods of each pod's
-    percentile (SimpleStrategySettings.cpu_aggregation); it needs a loader that keeps the pod
-    boundaries — "reference", or "bodies" with parser="host".  Calling it again
-    changes the switches;
+    percentile (SimpleStrategySettings.cpu_aggregation); every loader and parser keeps the pod
+    boundaries it needs ("reference", "bodies" and "grouped", parsed on the host, the device
+    or both).  Calling it again changes the switches;
     ``uninstall`` restores the reference's methods.  Returns the class."""
     if loader not in LOADERS:
         raise ValueError(f"loader must be one of {LOADERS}")

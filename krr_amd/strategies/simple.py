@@ -98,8 +98,9 @@ class SimpleStrategySettings(StrategySettings):
         """The kernel pass over a packed fleet.  ``cpu_aggregation`` "pods_max": each pod's
         percentile (any ``percentile_mode``) and the max over the object's pods, first maximal
         pod, one fused launch plus the fold (krr_simple_run_pods); the fleet's CPU series must
-        carry pod boundaries (every host packer writes them; the device packer does not:
-        ValueError).  NaN samples among the CPU values stay out of contract, as on the flat
+        carry pod boundaries: every packer attaches them, on the host (numpy) or, from the device
+        packer, as tensors in HBM that go to the kernels as they are; a PackedSeries built by
+        hand without them raises ValueError.  NaN samples among the CPU values stay out of contract, as on the flat
         path: a pod's KRR_FLAG_NAN is folded into the object's flags and ``cpu_from_raw``
         applies its rule with the folded count."""
         params = self.params()

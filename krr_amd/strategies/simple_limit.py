@@ -104,8 +104,9 @@ class SimpleLimitStrategySettings(StrategySettings):
         """One fused pass -> [RawResults at cpu_request, RawResults at cpu_limit] (they share
         the memory arrays).  ``cpu_aggregation`` "pods_max": request and limit per pod, each the
         max over the object's pods — its own first maximal pod — from one fused launch plus one
-        fold (krr_simple_run_pods_multi); the fleet's CPU series must carry pod boundaries (the
-        device packer writes none: ValueError).  NaN samples among the CPU values stay out of
+        fold (krr_simple_run_pods_multi); the fleet's CPU series must carry pod boundaries (every
+        packer attaches them, the device packer included; a series built by hand without them:
+        ValueError).  NaN samples among the CPU values stay out of
         contract, as in ``simple``: ``cpu_from_raw`` sees the folded flags and count."""
         params = self.params_list()
         engine = default_engine(self.device if device is None else device)
