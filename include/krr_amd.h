@@ -141,6 +141,29 @@ int krr_segmented_percentile(krr_ctx* ctx, const krr_series* series,
 int krr_segmented_max(krr_ctx* ctx, const krr_series* series, double* out_value,
                       int64_t* out_count, uint32_t* out_flags, void* stream);
 
+/* Per segment, ONE pass: count, min, max and sum of the present samples — the statistics a
+ * select cannot give, for strategies other than `simple` (mean plus headroom, baseline = min;
+ * krr_amd.api.batch.FleetBatch).  n = the present samples: every slot, or the non-NaN slots
+ * when gaps_are_nan.  Device pointers of n_segments entries; each of out_min / out_max /
+ * out_sum may be NULL and is then not written; out_count and out_flags are required.
+ *   - n == 0: KRR_FLAG_EMPTY, min = max = the quiet NaN, sum = +0.0;
+ *   - a NaN sample in the compact layout: KRR_FLAG_NAN, min = max = sum = the quiet NaN;
+ *   - out_max, out_count, out_flags: bit-identical to krr_segmented_max on the same series;
+ *   - out_min: the FIRST minimal element under float comparison, its own bits (-0.0 == +0.0:
+ *     the earlier one wins, Python min()'s rule);
+ *   - out_sum: the float64 sum of the present samples, plain IEEE and uncompensated: every
+ *     lane of the segment's wave adds the slots it meets, in order, to a running sum that
+ *     starts at +0.0, and the 64 lane sums are folded in one fixed order.  Any such order of
+ *     n - 1 additions errs by at most (n - 1) u / (1 - (n - 1) u) x sum|x|, u = 2^-53.  The
+ *     same buffers give the same bits on every launch; the order may depend on the PARITY of
+ *     the segment's start offset (an unaligned first or last sample is read with the last
+ *     chunk), so the same samples at another offset may sum to other last bits.  +Inf with
+ *     -Inf gives NaN with no flag, overflow gives +-Inf.
+ * KRR_E_INVALID: a null ctx or series, or out_count / out_flags NULL while n_segments > 0.
+ * n_segments == 0 launches nothing.  One wave per segment; no atomics, no LDS. */
+int krr_segmented_stats(krr_ctx* ctx, const krr_series* series, double* out_min, double* out_max,
+                        double* out_sum, int64_t* out_count, uint32_t* out_flags, void* stream);
+
 /* SimpleStrategy.run over every object: cpu and mem each hold one segment per
  * object (same n_segments).  Outputs are device pointers of n_segments entries. */
 int krr_simple_run(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,

@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "krr_last_error",
     "krr_segmented_percentile",
     "krr_segmented_max",
+    "krr_segmented_stats",
     "krr_simple_run",
     "krr_simple_run_records",
     "krr_simple_run_forward",
@@ -291,6 +292,8 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_segmented_percentile.restype = ctypes.c_int
         lib.krr_segmented_max.argtypes = [vp, sp, vp, vp, vp, vp]
         lib.krr_segmented_max.restype = ctypes.c_int
+        lib.krr_segmented_stats.argtypes = [vp, sp, vp, vp, vp, vp, vp, vp]
+        lib.krr_segmented_stats.restype = ctypes.c_int
         lib.krr_simple_run.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.restype = ctypes.c_int
@@ -482,6 +485,20 @@ class Context:
         self._check(self._lib.krr_segmented_max(
             self._h, ctypes.byref(series), out_value.data_ptr(), out_count.data_ptr(), out_flags.data_ptr(),
             self._stream(stream)))
+
+    def segmented_stats(self, series: KrrSeries, out_min, out_max, out_sum, out_count, out_flags,
+                        stream=None) -> None:
+        """Count, min, max and sum of every segment's present samples from one pass
+        (krr_segmented_stats): out_min / out_max / out_sum float64 [S], each optional (None: not
+        computed into a buffer); out_count int64 [S] and out_flags int32 [S] are required."""
+        for t in (out_min, out_max, out_sum):
+            if t is not None:
+                _check_tensor(t, "float64", series.n_segments)
+        _check_tensor(out_count, "int64", series.n_segments)
+        _check_tensor(out_flags, "int32", series.n_segments)
+        self._check(self._lib.krr_segmented_stats(
+            self._h, ctypes.byref(series), *(None if t is None else t.data_ptr() for t in (out_min, out_max, out_sum)),
+            out_count.data_ptr(), out_flags.data_ptr(), self._stream(stream)))
 
     def simple_run(self, cpu: KrrSeries, mem: KrrSeries, params: KrrPercentileParams, out: dict,
                    stream=None, records=None, forward=None) -> None:

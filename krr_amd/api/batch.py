@@ -1,0 +1,226 @@
+"""Fleet statistics for custom strategies: what a plugin's ``run_batch`` calls.
+
+``BatchedRunner.raw_results`` hands a strategy that implements ``run_batch(histories, objects)``
+the whole fleet at once.  ``FleetBatch`` turns that fleet into per-object float64 arrays computed
+on the device, one launch per statistic instead of a Python loop per object:
+
+    batch = FleetBatch(histories, device=0)        # packs each resource on first use, once
+    batch = FleetBatch.from_fleet(packed_fleet)    # a PackedFleet (e.g. BatchedRunner.pack_from_bodies)
+    st = batch.stats(ResourceType.Memory)          # FleetStats: count, min, max, sum, flags (+ .mean)
+    v = batch.percentile(ResourceType.Memory, "95", mode="sorted_lower")         # float64 [S]
+    vs = batch.percentiles(ResourceType.CPU, ["50", "95", "99"], mode="linear")  # float64 [P, S]
+    pods = batch.per_pod(ResourceType.CPU)         # a FleetBatch over one segment per pod + .pod_groups
+    batch.to_decimal(values, flags)                # list[Decimal]
+
+``stats`` is one krr_segmented_stats pass (min and max are the first minimal / maximal sample's own
+bits, Python ``min()`` / ``max()``; the sum is a plain float64 sum, include/krr_amd.h);
+``percentiles`` is krr_segmented_percentiles over ANY series, memory included, with the three
+rules of ``SimpleStrategySettings.percentile_mode``.  There is no CPU path: without the HIP
+library or a device every computing call raises ``NativeUnavailable``.
+
+Values are float64.  ``to_decimal`` gives each float's shortest string as a Decimal
+(``prom_decimal``: the Decimal the reference's loader parses from Prometheus).  For HistoryData
+whose Decimals are NOT Prometheus' strings ('0.10', 25-digit values: ``PackedSeries.exact``) that
+is an equal-valued or nearest Decimal, not the caller's own object; ``exact_mask`` names those
+objects so a strategy can send them through its per-object ``run()`` instead.
+"""
+from __future__ import annotations
+
+import decimal
+from dataclasses import dataclass
+from decimal import Decimal
+from typing import Mapping, Optional, Sequence
+
+import numpy as np
+
+from krr_amd import _native
+from krr_amd.core.engine import MODE_CODES, SimpleEngine, default_engine, percentile_params
+from krr_amd.core.models.allocations import ResourceType
+from krr_amd.core.packing import PackedFleet, PackedSeries, pack_resource, pod_view
+from krr_amd.utils.prom_decimal import prom_decimal
+
+__all__ = ["FleetBatch", "FleetStats"]
+
+
+@dataclass
+class FleetStats:
+    """Per-object statistics of one resource (host arrays, [S] each).  ``count`` is the present
+    samples; ``flags`` the kernels' KRR_FLAG_* (EMPTY: no sample, min = max = NaN and sum = 0;
+    NAN: a NaN sample, min = max = sum = NaN)."""
+    count: np.ndarray  # int64
+    min: np.ndarray    # float64
+    max: np.ndarray    # float64
+    sum: np.ndarray    # float64
+    flags: np.ndarray  # uint32
+
+    @property
+    def mean(self) -> np.ndarray:
+        """sum / count in float64; NaN where count == 0."""
+        out = np.full(self.count.shape, np.nan, dtype=np.float64)
+        np.divide(self.sum, self.count, out=out, where=self.count > 0)
+        return out
+
+
+class FleetBatch:
+    """A fleet's histories as device-side series, with cached per-object statistics.
+
+    Results are cached per (resource, call): asking twice launches once.  Not thread-safe (one
+    batch per ``run_batch`` call)."""
+
+    def __init__(self, histories: Optional[Sequence[Mapping]] = None, device: int = 0,
+                 engine: Optional[SimpleEngine] = None):
+        self._histories = histories if histories is not None else []
+        self._series: dict[ResourceType, PackedSeries] = {}
+        self._n = len(self._histories)
+        self.device = int(device)
+        self._engine = engine
+        self._cache: dict = {}
+        self.pod_groups: Optional[np.ndarray] = None  # per_pod() views: the pods of each object
+
+    @classmethod
+    def from_fleet(cls, fleet: PackedFleet, device: int = 0, engine: Optional[SimpleEngine] = None) -> "FleetBatch":
+        """Over a PackedFleet from any packer (host arrays, or tensors in HBM from the device
+        packer, which then run as they are): no Decimal lists at all."""
+        if fleet.cpu.n_segments != fleet.mem.n_segments:
+            raise ValueError("cpu and memory need one segment per object each")
+        return cls._of({ResourceType.CPU: fleet.cpu, ResourceType.Memory: fleet.mem}, fleet.n_objects, device, engine)
+
+    @classmethod
+    def _of(cls, series: dict, n: int, device: int, engine: Optional[SimpleEngine]) -> "FleetBatch":
+        batch = cls(None, device, engine)
+        batch._histories = None
+        batch._series = dict(series)
+        batch._n = int(n)
+        return batch
+
+    @property
+    def n_objects(self) -> int:
+        return self._n
+
+    @property
+    def engine(self) -> SimpleEngine:
+        if self._engine is None:
+            self._engine = default_engine(self.device)
+        return self._engine
+
+    def series(self, resource: ResourceType) -> PackedSeries:
+        """The resource's PackedSeries, packed on first use (pack_resource) and kept."""
+        resource = ResourceType(resource)
+        ps = self._series.get(resource)
+        if ps is None:
+            if self._histories is None:
+                raise KeyError(f"this batch holds no {resource.value} series")
+            ps = self._series[resource] = pack_resource(self._histories, resource)
+        return ps
+
+    # --- statistics --------------------------------------------------------------------
+    def stats(self, resource: ResourceType) -> FleetStats:
+        key = (ResourceType(resource), "stats")
+        st = self._cache.get(key)
+        if st is None:
+            r = self.engine.stats_series(self.series(resource))
+            st = self._cache[key] = FleetStats(r["count"], r["min"], r["max"], r["sum"], r["flags"])
+        return st
+
+    def percentiles(self, resource: ResourceType, percentiles: Sequence, mode: str = "ref_index",
+                    return_flags: bool = False):
+        """float64 [P, S]: row j is percentile ``percentiles[j]`` (anything ``cpu_percentile``
+        accepts: int, str, Decimal; 0 < p <= 100) of every object's series under ``mode``
+        ("ref_index": the sample at index int((n-1)·p/100) of the unsorted series; "sorted_lower":
+        sorted(x)[that index]; "linear": np.percentile).  No sample: NaN.  A NaN sample
+        (KRR_FLAG_NAN): NaN here, and ``to_decimal`` applies the reference's rule.
+        KRR_FLAG_CAPACITY raises RuntimeError.  ``return_flags``: also the uint32 [P, S] flags."""
+        if mode not in MODE_CODES:
+            raise ValueError(f"unknown percentile mode {mode!r}; expected one of {sorted(MODE_CODES)}")
+        resource = ResourceType(resource)
+        ps = [Decimal(str(p)) for p in percentiles]
+        keys = [(resource, "percentile", mode, p) for p in ps]
+        todo = [p for p, k in dict(zip(ps, keys)).items() if k not in self._cache]
+        if todo:
+            value, count, flags = self.engine.percentiles_series(self.series(resource),
+                                                                 [percentile_params(p, mode) for p in todo])
+            if (flags & _native.KRR_FLAG_CAPACITY).any():
+                j, s = np.argwhere(flags & _native.KRR_FLAG_CAPACITY)[0]
+                raise RuntimeError(f"object {s}: selection bound violated for percentile {todo[j]} (KRR_FLAG_CAPACITY)")
+            value = np.where(flags & _native.KRR_FLAG_NAN, np.nan, value)
+            for j, p in enumerate(todo):
+                self._cache[(resource, "percentile", mode, p)] = (value[j], flags[j], count)
+        rows = [self._cache[k] for k in keys]
+        S = self.series(resource).n_segments
+        value = np.stack([r[0] for r in rows]) if rows else np.zeros((0, S))
+        if return_flags:
+            return value, (np.stack([r[1] for r in rows]) if rows else np.zeros((0, S), dtype=np.uint32))
+        return value
+
+    def percentile(self, resource: ResourceType, percentile, mode: str = "ref_index", return_flags: bool = False):
+        """One percentile: float64 [S] (and, with ``return_flags``, uint32 [S])."""
+        out = self.percentiles(resource, [percentile], mode, return_flags)
+        return (out[0][0], out[1][0]) if return_flags else out[0]
+
+    def counts(self, resource: ResourceType, percentile, mode: str = "ref_index") -> np.ndarray:
+        """The present samples behind a percentile already asked for (int64 [S])."""
+        self.percentiles(resource, [percentile], mode)
+        return self._cache[(ResourceType(resource), "percentile", mode, Decimal(str(percentile)))][2]
+
+    # --- pods --------------------------------------------------------------------------
+    def per_pod(self, resource: ResourceType) -> "FleetBatch":
+        """A FleetBatch whose objects are the PODS of this one's, for that resource alone;
+        its ``pod_groups`` (int64 [S + 1], host) says which pods object s owns:
+        pod_groups[s] .. pod_groups[s + 1].  Raises ValueError for a series without pod
+        boundaries: ``FleetBatch(histories)`` (pack_resource) attaches them to the CPU series
+        only; the packers of response bodies keep them for every series they pack."""
+        resource = ResourceType(resource)
+        key = (resource, "per_pod")
+        pods = self._cache.get(key)
+        if pods is None:
+            ps = self.series(resource)
+            if ps.pod_offsets is None or ps.pod_groups is None:
+                pod_view(ps)  # raises the ValueError that names the packers
+            groups = ps.pod_groups
+            if isinstance(groups, np.ndarray) or not hasattr(groups, "is_cuda"):
+                view = pod_view(ps)
+                groups = np.asarray(groups, dtype=np.int64)
+            else:  # a series in HBM (device packer): its tensors go to the kernels as they are
+                po = ps.pod_offsets.contiguous()
+                longest = ps.pod_max_len
+                if longest is None:
+                    longest = int((po[1:] - po[:-1]).max()) if po.numel() > 1 else 0
+                view = PackedSeries(ps.values, po, int(longest), ps.gaps_are_nan)
+                groups = groups.cpu().numpy().astype(np.int64)
+            pods = self._cache[key] = FleetBatch._of({resource: view}, view.n_segments, self.device, self._engine)
+            pods.pod_groups = groups
+        return pods
+
+    # --- Decimals ----------------------------------------------------------------------
+    def exact_mask(self, resource: ResourceType) -> Optional[np.ndarray]:
+        """bool [S]: the objects whose Decimals are not Prometheus' own strings, so that
+        ``to_decimal`` cannot give back the caller's sample object; None when there is none
+        (always None for fleets packed from response bodies)."""
+        exact = self.series(resource).exact
+        return None if exact is None else np.asarray(exact) > 0
+
+    @staticmethod
+    def to_decimal(values, flags=None, counts=None, mode: Optional[str] = None) -> list:
+        """list[Decimal] of a float64 array: ``prom_decimal(float)``, the float's shortest
+        string.  With ``flags``, ``SimpleStrategySettings.cpu_from_raw``'s rule: KRR_FLAG_CAPACITY
+        raises RuntimeError, KRR_FLAG_EMPTY gives Decimal('NaN'), and KRR_FLAG_NAN gives
+        Decimal('NaN') — or, as the reference's sorted() / max() over Decimals would, raises
+        decimal.InvalidOperation when ``mode`` is "sorted_lower" and ``counts`` shows two or more
+        samples."""
+        values = np.asarray(values, dtype=np.float64)
+        if flags is None:
+            return [prom_decimal(float(v)) for v in values]
+        flags = np.asarray(flags).astype(np.uint32)
+        out = []
+        for i, (v, f) in enumerate(zip(values.tolist(), flags.tolist())):
+            if f & _native.KRR_FLAG_CAPACITY:
+                raise RuntimeError(f"object {i}: selection bound violated (KRR_FLAG_CAPACITY)")
+            if f & _native.KRR_FLAG_EMPTY:
+                out.append(Decimal("NaN"))
+            elif f & _native.KRR_FLAG_NAN:
+                if mode == "sorted_lower" and counts is not None and int(counts[i]) >= 2:
+                    raise decimal.InvalidOperation([decimal.InvalidOperation])
+                out.append(Decimal("NaN"))
+            else:
+                out.append(prom_decimal(v))
+        return out

@@ -308,6 +308,104 @@ class SimpleEngine:
         n = 1 if resident or nbytes <= 2 * self.chunk_bytes else -(-nbytes // self.chunk_bytes)
         return [(0, S)] if n == 1 else [(lo, hi) for lo, hi in fleet_shard_bounds(fleet, n) if hi > lo]
 
+    # --- one series at a time: the statistics behind krr_amd.api.batch.FleetBatch -----------
+    def stats_series(self, ps: PackedSeries) -> dict:
+        """Count, min, max and sum of every segment of one series (krr_segmented_stats): host
+        arrays ``min``, ``max``, ``sum`` (float64), ``count`` (int64) and ``flags`` (uint32),
+        [S] each.  A host series is uploaded and run in chunks of whole segments of about
+        ``chunk_bytes``; one already in HBM (device packer) runs as it is.  Every launch goes on
+        the current stream, with one synchronisation at the end."""
+        ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        parts = [self._stats_part(ctx, part) for part in self._series_parts(ps)]
+        host = self._host_concat(parts, {"min": np.float64, "max": np.float64, "sum": np.float64,
+                                         "count": np.int64, "flags": np.int32})
+        host["flags"] = host["flags"].view(np.uint32)
+        return host
+
+    def percentiles_series(self, ps: PackedSeries, params_list) -> tuple:
+        """Several percentiles of every segment of one series — CPU or memory — through
+        krr_segmented_percentiles: (value float64 [P, S], count int64 [S], flags uint32 [P, S]),
+        host arrays, row j for ``params_list[j]`` (entries of one mode).  Lists longer than
+        KRR_MAX_PERCENTILES run in groups; index tables are bound per launch from the chunk's
+        longest segment, as ``run_packed_multi`` binds them.  Chunks and synchronisation as
+        ``stats_series``."""
+        params_list = list(params_list)
+        if not params_list:
+            raise ValueError("at least one percentile")
+        ctx = self.context()
+        parts = [self._percentiles_part(ctx, part, params_list) for part in self._series_parts(ps)]
+        host = self._host_concat(parts, {"value": np.float64, "count": np.int64, "flags": np.int32},
+                                 rows={"value": len(params_list), "flags": len(params_list)})
+        return host["value"], host["count"], host["flags"].view(np.uint32)
+
+    def _series_parts(self, ps: PackedSeries):
+        """The whole-segment ranges one series runs as — ``_chunk_bounds``' rule for a single
+        resource: whole when resident in HBM or within two chunks of values, else
+        sample-balanced chunks of about ``chunk_bytes``."""
+        import torch
+
+        from krr_amd.core.distributed import shard_bounds, slice_series
+
+        S = ps.n_segments
+        if S == 0:
+            return
+        resident = isinstance(ps.values, torch.Tensor) and ps.values.is_cuda
+        nbytes = 0 if resident else 8 * int(ps.offsets[-1])
+        n = 1 if resident or nbytes <= 2 * self.chunk_bytes else -(-nbytes // self.chunk_bytes)
+        if n == 1:
+            yield ps
+            return
+        for lo, hi in shard_bounds(np.diff(ps.offsets), n):
+            if hi > lo:
+                yield slice_series(ps, lo, hi)
+
+    def _part_series(self, ctx, part: PackedSeries):
+        vals, offs = self._to_device(part)
+        return ctx.series(vals, offs, max(int(part.max_len), 1), part.gaps_are_nan)
+
+    def _stats_part(self, ctx, part: PackedSeries) -> dict:
+        """Upload (host series) and one krr_segmented_stats launch on the current stream: the
+        chunk's device tensors."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(self.device):
+            series = self._part_series(ctx, part)
+            n = part.n_segments
+            out = {k: torch.empty(n, dtype=dt, device=dev) for k, dt in
+                   (("min", torch.float64), ("max", torch.float64), ("sum", torch.float64),
+                    ("count", torch.int64), ("flags", torch.int32))}
+            ctx.segmented_stats(series, out["min"], out["max"], out["sum"], out["count"], out["flags"])
+        return out
+
+    def _percentiles_part(self, ctx, part: PackedSeries, params_list: list) -> dict:
+        """Upload (host series) and krr_segmented_percentiles per group of KRR_MAX_PERCENTILES
+        entries on the current stream: value / flags [P, n] and the shared count [n]."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        P, n, G = len(params_list), part.n_segments, _native.KRR_MAX_PERCENTILES
+        with torch.cuda.device(self.device):
+            series = self._part_series(ctx, part)
+            value = torch.empty((P, n), dtype=torch.float64, device=dev)
+            flags = torch.empty((P, n), dtype=torch.int32, device=dev)
+            count = torch.empty(n, dtype=torch.int64, device=dev)
+            for a in range(0, P, G):
+                ctx.segmented_percentiles(series, params_list[a:a + G], value[a:a + G], count, flags[a:a + G])
+        return {"value": value, "count": count, "flags": flags}
+
+    def _host_concat(self, parts: list, dtypes: dict, rows: Optional[dict] = None) -> dict:
+        """The chunks' tensors as host arrays, concatenated in segment order (the last axis);
+        synchronises the current stream once, before the first copy."""
+        import torch
+
+        rows = rows or {}
+        if not parts:  # a series without segments launches nothing
+            return {k: np.zeros((rows[k], 0) if k in rows else 0, dtype=dt) for k, dt in dtypes.items()}
+        if any(t.is_cuda for p in parts for t in p.values()):
+            torch.cuda.current_stream(self.device).synchronize()
+        return {k: np.concatenate([p[k].cpu().numpy() for p in parts], axis=-1) for k in dtypes}
+
     def run_packed_multi(self, fleet: PackedFleet, params_list, aggregation: str = "concat",
                          return_pods: bool = False) -> list:
         """Several CPU percentiles of a fleet (host- or device-packed) from one fused pass per

@@ -3178,6 +3178,92 @@ __global__ __launch_bounds__(64) void k_rank_of(const double* __restrict__ vals,
     }
 }
 
+// ------------------------------ STATS --------------------------------------
+// krr_segmented_stats: count, min, max and sum of every segment from ONE pass, for the
+// statistics a select cannot give (custom strategies: mean plus headroom, baseline = min).
+// v_max_f64 / v_min_f64 drop NaN slots (gaps, padding) by themselves; the sum takes 0.0
+// for them through a select, so every chunk runs the same branch-free body.  Each lane adds
+// its slots in the order it meets them, the wave then folds the 64 lane sums in wave_scan64's
+// fixed order: the same buffers give the same bits on every launch.
+struct StatsProc {
+    double mx, mn, sm;
+    uint32_t nn;
+    __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
+#pragma unroll
+        for (int j = 0; j < 2 * kUnroll; ++j) {
+            const double d = slot_val(c, j);
+            const bool nan = __builtin_isnan(d);
+            mx = fmax(mx, d);
+            mn = fmin(mn, d);
+            sm += nan ? 0.0 : d;
+            nn += popc64(ballot(nan));
+        }
+    }
+};
+
+struct OpAddF64Bits {
+    __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return dbits(bitsd(a) + bitsd(b)); }
+};
+__device__ __forceinline__ double wave_min_f64(double x) {
+    return bitsd(lane_bcast64(wave_scan64(dbits(x), kQuietNaN, OpMinF64Bits{}), kWave - 1));
+}
+__device__ __forceinline__ double wave_sum_f64(double x) {  // identity +0.0
+    return bitsd(lane_bcast64(wave_scan64(dbits(x), 0ull, OpAddF64Bits{}), kWave - 1));
+}
+
+struct StatsArgs {
+    const double* vals;
+    const int64_t* offs;
+    int64_t S;
+    int32_t gaps;
+    int32_t remap;  // xcd_item, chosen as max_args chooses it
+    double* out_min;  // may be null
+    double* out_max;  // may be null
+    double* out_sum;  // may be null
+    int64_t* out_n;
+    uint32_t* out_f;
+};
+
+__global__ __launch_bounds__(64) void k_stats(StatsArgs A) {
+    const int lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < A.S; b += gridDim.x) {
+        const int64_t s = xcd_item(b, A.S, A.remap);
+        const int64_t beg = A.offs[s], end = A.offs[s + 1];
+        StatsProc P{__builtin_nan(""), __builtin_nan(""), 0.0, 0u};
+        P.nn -= stream_segment<false>(A.vals, beg, end, P, lane);
+        const uint64_t L = (uint64_t)(end - beg);
+        const uint64_t n = A.gaps ? L - P.nn : L;
+        const double mx = wave_max_f64(P.mx), mn = wave_min_f64(P.mn), sm = wave_sum_f64(P.sm);
+        double rmax = bitsd(kQuietNaN), rmin = bitsd(kQuietNaN), rsum = 0.0;
+        uint32_t flags = 0;
+        if (n == 0) {
+            flags = KRR_FLAG_EMPTY;
+        } else if (P.nn && !A.gaps) {
+            flags = KRR_FLAG_NAN;
+            rsum = bitsd(kQuietNaN);
+        } else {
+            // Python max() / min() keep the FIRST extremal element; only +-0 compare equal with
+            // different bits, and an extremum of zero is the segment's first zero either way.
+            uint64_t bmax = uni64(dbits(mx)), bmin = uni64(dbits(mn));
+            if (is_zero_bits(bmax) || is_zero_bits(bmin)) {
+                const uint64_t z = nth_zero_bits(A.vals, beg, end, 0, lane);
+                if (is_zero_bits(bmax)) bmax = z;
+                if (is_zero_bits(bmin)) bmin = z;
+            }
+            rmax = bitsd(bmax);
+            rmin = bitsd(bmin);
+            rsum = sm;
+        }
+        if (lane == 0) {
+            if (A.out_min) A.out_min[s] = rmin;
+            if (A.out_max) A.out_max[s] = rmax;
+            if (A.out_sum) A.out_sum[s] = rsum;
+            A.out_n[s] = (int64_t)n;
+            A.out_f[s] = flags;
+        }
+    }
+}
+
 }  // namespace krr
 #include "krr_kll.h"
 namespace krr {
@@ -3891,6 +3977,24 @@ int krr_segmented_max(krr_ctx* ctx, const krr_series* series, double* out_value,
     if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
     const MaxArgs A = max_args(series, out_value, out_count, out_flags, nullptr);
     hipLaunchKernelGGL(k_max, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
+    KRR_HIP(ctx, hipGetLastError());
+    return KRR_OK;
+}
+
+int krr_segmented_stats(krr_ctx* ctx, const krr_series* series, double* out_min, double* out_max, double* out_sum,
+                        int64_t* out_count, uint32_t* out_flags, void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    int rc = check_series(ctx, series);
+    if (rc) return rc;
+    const int64_t S = series->n_segments;
+    if (S == 0) return KRR_OK;
+    if (!out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    const MaxArgs M = max_args(series, nullptr, out_count, out_flags, nullptr);  // its remap choice
+    const StatsArgs A{series->values, series->offsets, S,       series->gaps_are_nan, M.remap,
+                      out_min,        out_max,         out_sum, out_count,            out_flags};
+    hipLaunchKernelGGL(k_stats, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
     KRR_HIP(ctx, hipGetLastError());
     return KRR_OK;
 }
