@@ -164,6 +164,44 @@ int krr_segmented_max(krr_ctx* ctx, const krr_series* series, double* out_value,
 int krr_segmented_stats(krr_ctx* ctx, const krr_series* series, double* out_min, double* out_max,
                         double* out_sum, int64_t* out_count, uint32_t* out_flags, void* stream);
 
+/* Per segment, ONE pass: the mean and the centred second moments of the present samples and of
+ * their slot indices — what variance and a least-squares trend need (krr_amd.api.FleetMoments).
+ * Slot i = 0 .. L-1 is the offset from the segment's start (the packers keep no timestamps: the
+ * slot index is the time grid of the dense gapped layout and the sample index of the compact
+ * one); P = the present slots: every slot, or the non-NaN slots when gaps_are_nan; n = |P|.
+ *   mean  = (1/n) sum_P x_i             m2  = sum_P (x_i - mean)^2
+ *   tmean = (1/n) sum_P i               t2  = sum_P (i - tmean)^2
+ *   cxt   = sum_P (i - tmean)(x_i - mean)
+ * so that variance = m2 / n, slope = cxt / t2 and r^2 = cxt^2 / (t2 m2).  Never computed as
+ * sum x^2 - (sum x)^2 / n: every lane of the segment's wave centres the slots it holds of a
+ * chunk on their own mean (two passes over registers) and merges that into its running moments
+ * with Chan, Golub and LeVeque's update (delta = m_b - m_a, w = n_b / n: mean = m_a + delta w,
+ * M2 = M2_a + M2_b + delta^2 n_a w), and the 64 lanes' moments are merged the same way.
+ * With u = 2^-53, A = max|x|, Sxx = sum x^2, Sii = sum i^2 the errors are within
+ *   mean  n u A                         m2  n u sqrt(Sxx M2) + n^2 u^2 Sxx
+ *   tmean n u (L-1)                     t2  n u T2 + n^2 u^2 Sii
+ *   cxt   n u sqrt(Sxx T2) + n^2 u^2 sqrt(Sxx Sii)
+ * of the exact values (capitals).  Device pointers of n_segments entries.
+ *   - out_count, out_flags: bit-identical to krr_segmented_stats / krr_segmented_max;
+ *   - n == 0: KRR_FLAG_EMPTY, all five doubles the quiet NaN 0x7FF8000000000000;
+ *   - a NaN sample in the compact layout: KRR_FLAG_NAN, all five doubles the quiet NaN;
+ *   - n == 1: mean = the sample's own value, tmean = its slot index exactly,
+ *     m2 = t2 = cxt = +0.0;
+ *   - +-Inf samples or overflow: plain IEEE, no flag; mean and m2 come out non-finite (Inf or
+ *     NaN), tmean and t2 depend only on WHICH slots are present and stay finite;
+ *   - the same buffers give the same bits on every launch (no atomics, one fixed merge order);
+ *     as for krr_segmented_stats' sum, the order may depend on the PARITY of the segment's start
+ *     offset, so the same samples at another offset may give other last bits;
+ *   - out_tmean, out_t2 and out_cxt may be NULL all three together: the "no trend" launch, whose
+ *     out_mean and out_m2 are bit-identical to the full launch's at less arithmetic;
+ *   - out_mean and out_m2 may each be NULL and are then not written.
+ * KRR_E_INVALID: a null ctx or series; out_count / out_flags NULL, or only one or two of
+ * out_tmean / out_t2 / out_cxt NULL, while n_segments > 0.  n_segments == 0 launches nothing.
+ * One wave per segment; no atomics, no LDS. */
+int krr_segmented_moments(krr_ctx* ctx, const krr_series* series, double* out_mean, double* out_m2,
+                          double* out_tmean, double* out_t2, double* out_cxt, int64_t* out_count,
+                          uint32_t* out_flags, void* stream);
+
 /* SimpleStrategy.run over every object: cpu and mem each hold one segment per
  * object (same n_segments).  Outputs are device pointers of n_segments entries. */
 int krr_simple_run(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,

@@ -58,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "krr_segmented_percentile",
     "krr_segmented_max",
     "krr_segmented_stats",
+    "krr_segmented_moments",
     "krr_simple_run",
     "krr_simple_run_records",
     "krr_simple_run_forward",
@@ -294,6 +295,8 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_segmented_max.restype = ctypes.c_int
         lib.krr_segmented_stats.argtypes = [vp, sp, vp, vp, vp, vp, vp, vp]
         lib.krr_segmented_stats.restype = ctypes.c_int
+        lib.krr_segmented_moments.argtypes = [vp, sp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_segmented_moments.restype = ctypes.c_int
         lib.krr_simple_run.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.restype = ctypes.c_int
@@ -498,6 +501,26 @@ class Context:
         _check_tensor(out_flags, "int32", series.n_segments)
         self._check(self._lib.krr_segmented_stats(
             self._h, ctypes.byref(series), *(None if t is None else t.data_ptr() for t in (out_min, out_max, out_sum)),
+            out_count.data_ptr(), out_flags.data_ptr(), self._stream(stream)))
+
+    def segmented_moments(self, series: KrrSeries, out_mean, out_m2, out_tmean, out_t2, out_cxt, out_count,
+                          out_flags, stream=None) -> None:
+        """Mean and centred second moments of every segment's present samples and of their slot
+        indices from one pass (krr_segmented_moments): five float64 [S] outputs.  out_mean and
+        out_m2 are each optional (None: not written); out_tmean / out_t2 / out_cxt are given all
+        three or None all three (the launch without the trend); out_count int64 [S] and
+        out_flags int32 [S] are required."""
+        trend = (out_tmean, out_t2, out_cxt)
+        if any(t is None for t in trend) and not all(t is None for t in trend):
+            raise ValueError("out_tmean, out_t2 and out_cxt go together: all three or none")
+        for t in (out_mean, out_m2, *trend):
+            if t is not None:
+                _check_tensor(t, "float64", series.n_segments)
+        _check_tensor(out_count, "int64", series.n_segments)
+        _check_tensor(out_flags, "int32", series.n_segments)
+        self._check(self._lib.krr_segmented_moments(
+            self._h, ctypes.byref(series),
+            *(None if t is None else t.data_ptr() for t in (out_mean, out_m2, *trend)),
             out_count.data_ptr(), out_flags.data_ptr(), self._stream(stream)))
 
     def simple_run(self, cpu: KrrSeries, mem: KrrSeries, params: KrrPercentileParams, out: dict,

@@ -322,6 +322,19 @@ class SimpleEngine:
         host["flags"] = host["flags"].view(np.uint32)
         return host
 
+    def moments_series(self, ps: PackedSeries, trend: bool = True) -> dict:
+        """Mean and centred second moments of every segment of one series
+        (krr_segmented_moments): host arrays ``mean``, ``m2`` and, with ``trend``, ``tmean``,
+        ``t2``, ``cxt`` (float64), ``count`` (int64) and ``flags`` (uint32), [S] each.  Chunks
+        and synchronisation as ``stats_series``: segments never span chunks, so the chunks'
+        results are concatenated and nothing is merged across them."""
+        ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        parts = [self._moments_part(ctx, part, trend) for part in self._series_parts(ps)]
+        dtypes = {k: np.float64 for k in (("mean", "m2", "tmean", "t2", "cxt") if trend else ("mean", "m2"))}
+        host = self._host_concat(parts, {**dtypes, "count": np.int64, "flags": np.int32})
+        host["flags"] = host["flags"].view(np.uint32)
+        return host
+
     def percentiles_series(self, ps: PackedSeries, params_list) -> tuple:
         """Several percentiles of every segment of one series — CPU or memory — through
         krr_segmented_percentiles: (value float64 [P, S], count int64 [S], flags uint32 [P, S]),
@@ -376,6 +389,23 @@ class SimpleEngine:
                    (("min", torch.float64), ("max", torch.float64), ("sum", torch.float64),
                     ("count", torch.int64), ("flags", torch.int32))}
             ctx.segmented_stats(series, out["min"], out["max"], out["sum"], out["count"], out["flags"])
+        return out
+
+    def _moments_part(self, ctx, part: PackedSeries, trend: bool) -> dict:
+        """Upload (host series) and one krr_segmented_moments launch on the current stream: the
+        chunk's device tensors (without ``trend``: no tmean / t2 / cxt)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(self.device):
+            series = self._part_series(ctx, part)
+            n = part.n_segments
+            names = ("mean", "m2", "tmean", "t2", "cxt") if trend else ("mean", "m2")
+            out = {k: torch.empty(n, dtype=torch.float64, device=dev) for k in names}
+            out["count"] = torch.empty(n, dtype=torch.int64, device=dev)
+            out["flags"] = torch.empty(n, dtype=torch.int32, device=dev)
+            ctx.segmented_moments(series, out["mean"], out["m2"], out.get("tmean"), out.get("t2"), out.get("cxt"),
+                                  out["count"], out["flags"])
         return out
 
     def _percentiles_part(self, ctx, part: PackedSeries, params_list: list) -> dict:

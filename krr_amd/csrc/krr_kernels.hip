@@ -3264,6 +3264,198 @@ __global__ __launch_bounds__(64) void k_stats(StatsArgs A) {
     }
 }
 
+// ------------------------------ MOMENTS ------------------------------------
+// krr_segmented_moments: per segment the mean and the centred second moments of the samples x
+// and of their slot indices t (t = offset from the segment's start): what variance and a
+// least-squares trend need, from ONE pass and without the cancellation of sum-of-squares
+// formulas.  A tuple (n, mean, M2[, tmean, T2, C]) describes any set of slots; two tuples of
+// disjoint sets merge with Chan, Golub and LeVeque's update (mom_merge).  A lane turns the 16
+// slots it holds of a chunk into a tuple with a local two-pass (means first, then the centred
+// products over the same registers; absent slots contribute 0 through selects), merges it into
+// its running tuple, and the wave folds the 64 lane tuples in wave_scan64's fixed DPP order: no
+// atomics, the same buffers give the same bits on every launch.  The file is compiled with
+// contraction off, so the TREND and no-TREND instantiations run the same mean / M2 arithmetic.
+struct Mom {
+    double n, mx, m2;  // present slots (an exact integer), mean and sum (x - mean)^2
+    double mt, t2, c;  // TREND: mean of t, sum (t - tmean)^2, sum (t - tmean)(x - mean)
+};
+
+// The tuple of a's slots followed by b's; an empty side (n == 0) is the exact identity.
+template <bool TREND>
+__device__ __forceinline__ Mom mom_merge(const Mom& a, const Mom& b) {
+    const bool ea = a.n == 0.0, eb = b.n == 0.0;
+    const double n = a.n + b.n;
+    const double w = b.n / (n > 0.0 ? n : 1.0);
+    const double q = a.n * w;
+    const double dx = b.mx - a.mx;
+    Mom r;
+    r.n = n;
+    const double mx = a.mx + dx * w;
+    const double m2 = (a.m2 + b.m2) + (dx * dx) * q;
+    r.mx = ea ? b.mx : eb ? a.mx : mx;
+    r.m2 = ea ? b.m2 : eb ? a.m2 : m2;
+    if constexpr (TREND) {
+        const double dt = b.mt - a.mt;
+        const double mt = a.mt + dt * w;
+        const double t2 = (a.t2 + b.t2) + (dt * dt) * q;
+        const double c = (a.c + b.c) + (dx * dt) * q;
+        r.mt = ea ? b.mt : eb ? a.mt : mt;
+        r.t2 = ea ? b.t2 : eb ? a.t2 : t2;
+        r.c = ea ? b.c : eb ? a.c : c;
+    } else {
+        r.mt = r.t2 = r.c = 0.0;
+    }
+    return r;
+}
+
+// proc.chunk(c) carries no position, so the processor rebuilds stream_segment's geometry from
+// beg / end and counts its chunks: in chunk ci lane l holds, in c[u], the slots
+// a0 - beg + 2 (ci CH + u kWave + l) and the next one, and in the partial last chunk lane 63's
+// c[kUnroll - 1] holds the unaligned head (slot 0) in .x and the unaligned tail (slot L - 1)
+// in .y.  Padding is NaN and therefore absent.
+template <bool TREND>
+struct MomentsProc {
+    Mom run;
+    double t0;     // slot index of c[0].x in the chunk to come
+    double tlast;  // L - 1
+    int64_t full;  // full chunks still to come before the partial one
+    bool last_lane;
+    __device__ __forceinline__ MomentsProc(int64_t beg, int64_t end, int lane) {
+        int64_t a0 = (beg + 1) & ~(int64_t)1;
+        if (a0 > end) a0 = end;
+        int64_t a1 = end & ~(int64_t)1;
+        if (a1 < a0) a1 = a0;
+        full = ((a1 >> 1) - (a0 >> 1)) / (kUnroll * kWave);
+        t0 = (double)(a0 - beg + 2 * lane);
+        tlast = (double)(end - beg - 1);
+        last_lane = lane == kWave - 1;
+        run = Mom{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    }
+    __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
+        constexpr int N = 2 * kUnroll;
+        const bool edge = full == 0 && last_lane;  // this lane's last unit is (head, tail)
+        // slot index of slot j: rebuilt where it is used (an exact sum), not held in 32 VGPRs
+        auto t = [&](int j) {
+            const double tj = t0 + (double)((j >> 1) * 2 * kWave + (j & 1));
+            return j == N - 2 ? (edge ? 0.0 : tj) : j == N - 1 ? (edge ? tlast : tj) : tj;
+        };
+        double k = 0.0, sx = -0.0, st = 0.0;  // -0.0: a lone -0.0 sample keeps its sign
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const double d = slot_val(c, j);
+            const bool p = !__builtin_isnan(d);
+            k += p ? 1.0 : 0.0;
+            sx += p ? d : -0.0;
+            if constexpr (TREND) st += p ? t(j) : 0.0;
+        }
+        const double kd = k > 0.0 ? k : 1.0;
+        Mom b;
+        b.n = k;
+        b.mx = sx / kd;
+        b.m2 = 0.0;
+        b.mt = TREND ? st / kd : 0.0;
+        b.t2 = b.c = 0.0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const double d = slot_val(c, j);
+            const bool p = !__builtin_isnan(d);
+            const double dx = p ? d - b.mx : 0.0;
+            b.m2 += dx * dx;
+            if constexpr (TREND) {
+                const double dt = p ? t(j) - b.mt : 0.0;
+                b.t2 += dt * dt;
+                b.c += dx * dt;
+            }
+        }
+        run = mom_merge<TREND>(run, b);
+        t0 += (double)(2 * kUnroll * kWave);
+        --full;
+    }
+};
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_f64(double x) {  // lanes nothing is shifted into read 0.0
+    return bitsd(dpp64<CTRL, ROW_MASK>(0ull, dbits(x)));
+}
+template <bool TREND, int CTRL, int ROW_MASK>
+__device__ __forceinline__ Mom mom_step(const Mom& x) {  // (tuple of the earlier lanes) merge x
+    Mom a;
+    a.n = dpp_f64<CTRL, ROW_MASK>(x.n);  // 0.0: the empty tuple
+    a.mx = dpp_f64<CTRL, ROW_MASK>(x.mx);
+    a.m2 = dpp_f64<CTRL, ROW_MASK>(x.m2);
+    a.mt = TREND ? dpp_f64<CTRL, ROW_MASK>(x.mt) : 0.0;
+    a.t2 = TREND ? dpp_f64<CTRL, ROW_MASK>(x.t2) : 0.0;
+    a.c = TREND ? dpp_f64<CTRL, ROW_MASK>(x.c) : 0.0;
+    return mom_merge<TREND>(a, x);
+}
+// The wave's 64 lane tuples in lane order, merged along wave_scan64's tree; uniform result.
+template <bool TREND>
+__device__ __forceinline__ Mom wave_moments(Mom x) {
+    x = mom_step<TREND, kDppRowShr1, 0xF>(x);
+    x = mom_step<TREND, kDppRowShr2, 0xF>(x);
+    x = mom_step<TREND, kDppRowShr4, 0xF>(x);
+    x = mom_step<TREND, kDppRowShr8, 0xF>(x);
+    x = mom_step<TREND, kDppRowBcast15, 0xA>(x);
+    x = mom_step<TREND, kDppRowBcast31, 0xC>(x);
+    auto last = [](double v) { return bitsd(lane_bcast64(dbits(v), kWave - 1)); };
+    return Mom{last(x.n), last(x.mx), last(x.m2), TREND ? last(x.mt) : 0.0, TREND ? last(x.t2) : 0.0,
+               TREND ? last(x.c) : 0.0};
+}
+
+struct MomentsArgs {
+    const double* vals;
+    const int64_t* offs;
+    int64_t S;
+    int32_t gaps;
+    int32_t remap;     // xcd_item, chosen as max_args chooses it
+    double* out_mean;  // may be null
+    double* out_m2;    // may be null
+    double* out_tmean;  // TREND: required
+    double* out_t2;
+    double* out_cxt;
+    int64_t* out_n;
+    uint32_t* out_f;
+};
+
+// The TREND body is large, so it takes the skeleton's single-site loop (one inlined chunk body,
+// one chunk in flight beyond the one processed): 154 VGPRs and 3 waves per SIMD.  Through the
+// three-buffer loop k_stats uses it needs 254 VGPRs + 8 AGPRs, runs 1 wave per SIMD and took
+// 1.47x k_stats' time on the config-3 memory shape against 1.00-1.01x this way
+// (profiles/moments/variants.md).  The chunks arrive in the same order either way, so the loop
+// does not change a bit of the result.  The no-TREND body stays on k_stats' loop.
+#ifndef KRR_MOMENTS_ONE_SITE
+#define KRR_MOMENTS_ONE_SITE 1
+#endif
+template <bool TREND>
+__global__ __launch_bounds__(64) void k_moments(MomentsArgs A) {
+    const int lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < A.S; b += gridDim.x) {
+        const int64_t s = xcd_item(b, A.S, A.remap);
+        const int64_t beg = A.offs[s], end = A.offs[s + 1];
+        MomentsProc<TREND> P(beg, end, lane);
+        stream_segment<(KRR_MOMENTS_ONE_SITE && TREND)>(A.vals, beg, end, P, lane);
+        const Mom m = wave_moments<TREND>(P.run);
+        const uint64_t L = (uint64_t)(end - beg);
+        const uint64_t present = (uint64_t)m.n;  // the non-NaN slots: padding is NaN too
+        const uint64_t n = A.gaps ? present : L;
+        const double qnan = bitsd(kQuietNaN);
+        uint32_t flags = 0;
+        if (n == 0) flags = KRR_FLAG_EMPTY;
+        else if (present != L && !A.gaps) flags = KRR_FLAG_NAN;
+        if (lane == 0) {
+            if (A.out_mean) A.out_mean[s] = flags ? qnan : m.mx;
+            if (A.out_m2) A.out_m2[s] = flags ? qnan : m.m2;
+            if constexpr (TREND) {
+                A.out_tmean[s] = flags ? qnan : m.mt;
+                A.out_t2[s] = flags ? qnan : m.t2;
+                A.out_cxt[s] = flags ? qnan : m.c;
+            }
+            A.out_n[s] = (int64_t)n;
+            A.out_f[s] = flags;
+        }
+    }
+}
+
 }  // namespace krr
 #include "krr_kll.h"
 namespace krr {
@@ -3995,6 +4187,29 @@ int krr_segmented_stats(krr_ctx* ctx, const krr_series* series, double* out_min,
     const StatsArgs A{series->values, series->offsets, S,       series->gaps_are_nan, M.remap,
                       out_min,        out_max,         out_sum, out_count,            out_flags};
     hipLaunchKernelGGL(k_stats, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
+    KRR_HIP(ctx, hipGetLastError());
+    return KRR_OK;
+}
+
+int krr_segmented_moments(krr_ctx* ctx, const krr_series* series, double* out_mean, double* out_m2,
+                          double* out_tmean, double* out_t2, double* out_cxt, int64_t* out_count,
+                          uint32_t* out_flags, void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    int rc = check_series(ctx, series);
+    if (rc) return rc;
+    const int64_t S = series->n_segments;
+    if (S == 0) return KRR_OK;
+    if (!out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+    const int n_trend = (out_tmean != nullptr) + (out_t2 != nullptr) + (out_cxt != nullptr);
+    if (n_trend != 0 && n_trend != 3)
+        return set_err(ctx, KRR_E_INVALID, "out_tmean, out_t2 and out_cxt go together%s", "");
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    const MaxArgs M = max_args(series, nullptr, out_count, out_flags, nullptr);  // its remap choice
+    const MomentsArgs A{series->values, series->offsets, S,      series->gaps_are_nan, M.remap,   out_mean,
+                        out_m2,         out_tmean,       out_t2, out_cxt,              out_count, out_flags};
+    if (n_trend) hipLaunchKernelGGL(k_moments<true>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(k_moments<false>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
     KRR_HIP(ctx, hipGetLastError());
     return KRR_OK;
 }
