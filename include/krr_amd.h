@@ -202,6 +202,50 @@ int krr_segmented_moments(krr_ctx* ctx, const krr_series* series, double* out_me
                           double* out_tmean, double* out_t2, double* out_cxt, int64_t* out_count,
                           uint32_t* out_flags, void* stream);
 
+/* Per segment and threshold, ONE pass over the series whatever n_thresholds: how many samples
+ * lie above the threshold, by how much, and for how long at a stretch (krr_amd.api
+ * .FleetExceedance).  thresholds and the six per-threshold outputs are row-major
+ * [n_thresholds * n_segments]: row r holds threshold r of every segment; out_count and out_flags
+ * are [n_segments] and shared by the rows.  All pointers are device pointers.
+ * For segment s and row r, tau = thresholds[r * n_segments + s]; P = the present slots in slot
+ * order: every slot, or the non-NaN slots when gaps_are_nan.
+ *   - a sample is ABOVE when x > tau, the float comparison, strict: a sample equal to tau is
+ *     not above, and +0.0 > -0.0 is false;
+ *   - an absent slot is transparent: it is not counted and does not end a run.  A run is a
+ *     maximal sequence of consecutive present samples that are all above.  Consequently every
+ *     integer output except out_last equals what the compacted series (P's samples packed
+ *     without the absent slots) gives.
+ *   above   = the number of samples of P above tau
+ *   excess  = sum of (x_i - tau) over the above samples: a plain IEEE float64 sum in one fixed
+ *             order, +0.0 when nothing is above.  Each term is one rounded subtraction and the
+ *             terms are non-negative, so with m = above, u = 2^-53 and E the exact sum the error
+ *             is within  m u / (1 - m u) * E  (derived, not measured).  The bits of row r do not
+ *             depend on n_thresholds or on the other rows
+ *   longest = the length of the longest run
+ *   head    = the length of the run that starts at P's first sample, 0 if it is not above
+ *   tail    = the length of the run that ends at P's last sample, 0 if it is not above; head and
+ *             tail make two results of adjacent series mergeable
+ *   last    = the slot index (offset from the segment's start, absent slots included) of the
+ *             last above sample, -1 if none
+ *   - out_count, out_flags: bit-identical to krr_segmented_stats on the same series;
+ *   - KRR_FLAG_EMPTY: integers 0, last -1, excess +0.0;
+ *   - KRR_FLAG_NAN (a NaN sample in the compact layout): excess the quiet NaN
+ *     0x7FF8000000000000, integers 0, last -1;
+ *   - tau = NaN or +Inf: nothing is above, no flag ("no request set");
+ *   - tau = -Inf: every present sample is above, excess +Inf (plain IEEE);
+ *   - the same buffers give the same bits on every launch (no atomics, one fixed order); as for
+ *     krr_segmented_stats' sum the order may depend on the parity of the segment's start offset.
+ * Each of the six per-threshold outputs may be NULL and is then not written.
+ * KRR_E_INVALID: a null ctx or series; n_thresholds outside 1..KRR_MAX_THRESHOLDS; thresholds,
+ * out_count or out_flags NULL, while n_segments > 0.  n_segments == 0 launches nothing.
+ * One wave per segment; no atomics, no LDS.  The running counts are 32-bit, as
+ * krr_segmented_stats' NaN count is: segments of fewer than 2^32 slots. */
+#define KRR_MAX_THRESHOLDS 4
+int krr_segmented_exceed(krr_ctx* ctx, const krr_series* series, const double* thresholds,
+                         int32_t n_thresholds, int64_t* out_above, double* out_excess,
+                         int64_t* out_longest, int64_t* out_head, int64_t* out_tail, int64_t* out_last,
+                         int64_t* out_count, uint32_t* out_flags, void* stream);
+
 /* SimpleStrategy.run over every object: cpu and mem each hold one segment per
  * object (same n_segments).  Outputs are device pointers of n_segments entries. */
 int krr_simple_run(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,

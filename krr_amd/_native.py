@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "krr_segmented_max",
     "krr_segmented_stats",
     "krr_segmented_moments",
+    "krr_segmented_exceed",
     "krr_simple_run",
     "krr_simple_run_records",
     "krr_simple_run_forward",
@@ -233,6 +234,7 @@ class KrrSelectPlanInfo(ctypes.Structure):
 
 
 KRR_MAX_PERCENTILES = 4
+KRR_MAX_THRESHOLDS = 4  # krr_segmented_exceed: thresholds per launch
 
 
 class KrrMultiPlanInfo(ctypes.Structure):
@@ -297,6 +299,8 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_segmented_stats.restype = ctypes.c_int
         lib.krr_segmented_moments.argtypes = [vp, sp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_segmented_moments.restype = ctypes.c_int
+        lib.krr_segmented_exceed.argtypes = [vp, sp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_segmented_exceed.restype = ctypes.c_int
         lib.krr_simple_run.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.restype = ctypes.c_int
@@ -522,6 +526,28 @@ class Context:
             self._h, ctypes.byref(series),
             *(None if t is None else t.data_ptr() for t in (out_mean, out_m2, *trend)),
             out_count.data_ptr(), out_flags.data_ptr(), self._stream(stream)))
+
+    def segmented_exceed(self, series: KrrSeries, thresholds, n_thresholds: int, above, excess, longest, head,
+                         tail, last, count, flags, stream=None) -> None:
+        """Per segment and threshold: samples above it, their summed excess, the longest run and
+        the runs at the segment's two ends, and the slot of the last sample above
+        (krr_segmented_exceed), from one pass whatever ``n_thresholds`` (1..KRR_MAX_THRESHOLDS).
+        ``thresholds`` float64 and the six outputs (``excess`` float64, the others int64) are
+        row-major [n_thresholds * S]; each output is optional (None: not written).  ``count``
+        int64 [S] and ``flags`` int32 [S] are required."""
+        n_thresholds = int(n_thresholds)
+        rows = max(n_thresholds, 0) * series.n_segments
+        _check_tensor(thresholds, "float64", rows)
+        for t, dt in ((above, "int64"), (excess, "float64"), (longest, "int64"), (head, "int64"), (tail, "int64"),
+                      (last, "int64")):
+            if t is not None:
+                _check_tensor(t, dt, rows)
+        _check_tensor(count, "int64", series.n_segments)
+        _check_tensor(flags, "int32", series.n_segments)
+        self._check(self._lib.krr_segmented_exceed(
+            self._h, ctypes.byref(series), thresholds.data_ptr(), n_thresholds,
+            *(None if t is None else t.data_ptr() for t in (above, excess, longest, head, tail, last)),
+            count.data_ptr(), flags.data_ptr(), self._stream(stream)))
 
     def simple_run(self, cpu: KrrSeries, mem: KrrSeries, params: KrrPercentileParams, out: dict,
                    stream=None, records=None, forward=None) -> None:

@@ -8,6 +8,8 @@ on the device, one launch per statistic instead of a Python loop per object:
     batch = FleetBatch.from_fleet(packed_fleet)    # a PackedFleet (e.g. BatchedRunner.pack_from_bodies)
     st = batch.stats(ResourceType.Memory)          # FleetStats: count, min, max, sum, flags (+ .mean)
     mo = batch.moments(ResourceType.Memory)        # FleetMoments: mean, m2, trend (+ .std(), .slope, ...)
+    ex = batch.exceedance(ResourceType.CPU, allocation_thresholds(objects, ResourceType.CPU))
+                                                   # FleetExceedance: above, excess, longest run, ... per threshold
     v = batch.percentile(ResourceType.Memory, "95", mode="sorted_lower")         # float64 [S]
     vs = batch.percentiles(ResourceType.CPU, ["50", "95", "99"], mode="linear")  # float64 [P, S]
     pods = batch.per_pod(ResourceType.CPU)         # a FleetBatch over one segment per pod + .pod_groups
@@ -40,7 +42,7 @@ from krr_amd.core.models.allocations import ResourceType
 from krr_amd.core.packing import PackedFleet, PackedSeries, pack_resource, pod_view
 from krr_amd.utils.prom_decimal import prom_decimal
 
-__all__ = ["FleetBatch", "FleetMoments", "FleetStats"]
+__all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetStats", "allocation_thresholds"]
 
 
 @dataclass
@@ -169,6 +171,101 @@ class FleetMoments:
         return FleetMoments(self.count + other.count, mean, m2, tmean, t2, cxt, flags, self.slots + other.slots)
 
 
+def _same_bits(a: np.ndarray, b: np.ndarray) -> bool:
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return a.shape == b.shape and bool(((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))).all())
+
+
+@dataclass
+class FleetExceedance:
+    """Per object and threshold, how the samples lie above the threshold (host arrays): what
+    "how often, and for how long at a stretch, was usage above this number?" needs, and mergeable
+    (``concat``).  A sample is above when ``x > threshold`` (strict); a threshold of NaN or +Inf
+    has nothing above it ("no request set").  Absent slots of the gapped layout are transparent:
+    they neither count nor end a run, so a run is a sequence of consecutive PRESENT samples that
+    are all above.
+
+    [R, S], row r for ``thresholds[r]``: ``above`` (samples above), ``excess`` (sum of x -
+    threshold over them, float64: "core-slots over the request"), ``longest`` (longest run),
+    ``head`` / ``tail`` (the runs at the series' first / last present sample; ``tail`` is
+    "currently over for this many samples"), ``last`` (slot of the last sample above, -1 if none).
+    [S]: ``count`` (present samples), ``flags`` (the kernels' KRR_FLAG_*: EMPTY: no sample; NAN: a
+    NaN sample, then ``excess`` is NaN and the integers are 0), ``slots`` (each series' length)."""
+    above: np.ndarray       # int64 [R, S]
+    excess: np.ndarray      # float64 [R, S]
+    longest: np.ndarray     # int64 [R, S]
+    head: np.ndarray        # int64 [R, S]
+    tail: np.ndarray        # int64 [R, S]
+    last: np.ndarray        # int64 [R, S]
+    thresholds: np.ndarray  # float64 [R, S]
+    count: np.ndarray       # int64 [S]
+    flags: np.ndarray       # uint32 [S]
+    slots: np.ndarray       # int64 [S]
+
+    @property
+    def share(self) -> np.ndarray:
+        """above / count: the part of the samples above the threshold; NaN where count == 0."""
+        out = np.full(self.above.shape, np.nan, dtype=np.float64)
+        np.divide(self.above, self.count, out=out, where=np.broadcast_to(self.count > 0, self.above.shape))
+        return out
+
+    @property
+    def mean_excess(self) -> np.ndarray:
+        """excess / above: how far above the threshold a breaching sample lies on average; NaN
+        where nothing is above."""
+        out = np.full(self.above.shape, np.nan, dtype=np.float64)
+        np.divide(self.excess, self.above, out=out, where=self.above > 0)
+        return out
+
+    @property
+    def since_last(self) -> np.ndarray:
+        """slots - 1 - last: the slots since the last sample above; -1 where there is none."""
+        return np.where(self.last >= 0, self.slots - 1 - self.last, -1)
+
+    def concat(self, other: "FleetExceedance") -> "FleetExceedance":
+        """The result of each series followed by ``other``'s (``other``'s slot i becomes slot
+        ``self.slots + i``), from the two results alone: counts and excess add, and the runs
+        merge as run statistics do,
+
+            head = self.head == self.count ? self.count + other.head : self.head
+            tail = other.tail == other.count ? other.count + self.tail : other.tail
+            longest = max(self.longest, other.longest, self.tail + other.head)
+
+        with an empty side the identity.  ``last`` is ``self.slots + other.last`` where ``other``
+        has a sample above, else ``self.last``.  Flags are OR-ed, except EMPTY, which survives
+        only where both sides are empty.  Raises ValueError unless both sides hold the same
+        objects and bitwise the same thresholds (NaN equals NaN)."""
+        if self.count.shape != other.count.shape or self.above.shape != other.above.shape:
+            raise ValueError("concat needs the same objects and thresholds on both sides")
+        if not _same_bits(self.thresholds, other.thresholds):
+            raise ValueError("concat needs bitwise the same thresholds on both sides")
+        na, nb = self.count, other.count
+        head = np.where(self.head == na, na + other.head, self.head)
+        tail = np.where(other.tail == nb, nb + self.tail, other.tail)
+        longest = np.maximum(np.maximum(self.longest, other.longest), self.tail + other.head)
+        last = np.where(other.last >= 0, self.slots + other.last, self.last)
+        empty = np.uint32(_native.KRR_FLAG_EMPTY)
+        fa, fb = self.flags.astype(np.uint32), other.flags.astype(np.uint32)
+        flags = ((fa | fb) & ~empty) | (fa & fb & empty)
+        return FleetExceedance(self.above + other.above, self.excess + other.excess, longest, head, tail, last,
+                               self.thresholds, na + nb, flags, self.slots + other.slots)
+
+
+def allocation_thresholds(objects: Sequence, resource: ResourceType, which: str = "requests") -> np.ndarray:
+    """float64 [S]: each object's current request (or, ``which="limits"``, limit) of ``resource``
+    from ``K8sObjectData.allocations``, as a threshold row for ``FleetBatch.exceedance``.  An
+    allocation that is not set (None) or not known ("?") becomes NaN: nothing is above it."""
+    if which not in ("requests", "limits"):
+        raise ValueError(f"which must be 'requests' or 'limits', got {which!r}")
+    resource = ResourceType(resource)
+    out = np.full(len(objects), np.nan, dtype=np.float64)
+    for i, obj in enumerate(objects):
+        v = getattr(obj.allocations, which).get(resource)
+        if v is not None and v != "?":
+            out[i] = float(v)
+    return out
+
+
 class FleetBatch:
     """A fleet's histories as device-side series, with cached per-object statistics.
 
@@ -249,6 +346,52 @@ class FleetBatch:
             mo = self._cache[(resource, "moments", bool(trend))] = FleetMoments(
                 r["count"], r["mean"], r["m2"], r.get("tmean"), r.get("t2"), r.get("cxt"), r["flags"], slots)
         return mo
+
+    def _threshold_rows(self, thresholds, S: int) -> np.ndarray:
+        """``exceedance``'s thresholds as contiguous float64 [R, S]."""
+        if isinstance(thresholds, np.ndarray) and thresholds.dtype != object:
+            thr = thresholds.astype(np.float64, copy=False)
+        else:
+            seq = list(thresholds)
+            if any(isinstance(t, (list, tuple, np.ndarray)) for t in seq):
+                raise ValueError("thresholds given as a sequence hold one scalar per object (Decimal, float or None); "
+                                 "several thresholds per object go in a float64 array [R, S]")
+            thr = np.array([np.nan if t is None else float(t) for t in seq], dtype=np.float64)
+        if thr.ndim == 1:
+            thr = thr[None, :]
+        if thr.ndim != 2 or thr.shape[0] < 1 or thr.shape[1] != S:
+            raise ValueError(f"thresholds must have shape [{S}] or [R, {S}] with R >= 1 (one column per object), "
+                             f"got {thr.shape}")
+        return np.ascontiguousarray(thr)
+
+    def exceedance(self, resource: ResourceType, thresholds) -> FleetExceedance:
+        """How every object's series lies above its thresholds: samples above, their summed
+        excess, the longest run and the runs at both ends (FleetExceedance), from one
+        krr_segmented_exceed pass per four thresholds.  ``thresholds`` is float64 [S] (one per
+        object), float64 [R, S] (R per object; the result's rows), or a sequence with one
+        ``Decimal | float | None`` per object, where None and Decimal('NaN') become NaN: "no
+        request set", nothing is above it.  ``allocation_thresholds(objects, resource)`` builds
+        the row of current requests or limits.  Cached per (resource, threshold bytes).
+
+        On a ``per_pod()`` view the objects are pods; per-object thresholds go to the pods with
+
+            pods = batch.per_pod(ResourceType.CPU)
+            ex = pods.exceedance(ResourceType.CPU, np.repeat(thr, np.diff(pods.pod_groups)))
+        """
+        resource = ResourceType(resource)
+        ps = self.series(resource)
+        thr = self._threshold_rows(thresholds, ps.n_segments)
+        key = (resource, "exceedance", thr.shape[0], thr.tobytes())
+        ex = self._cache.get(key)
+        if ex is None:
+            r = self.engine.exceed_series(ps, thr)
+            offs = ps.offsets
+            if not isinstance(offs, np.ndarray) and hasattr(offs, "is_cuda"):
+                offs = offs.cpu().numpy()
+            slots = np.diff(np.asarray(offs, dtype=np.int64))
+            ex = self._cache[key] = FleetExceedance(r["above"], r["excess"], r["longest"], r["head"], r["tail"],
+                                                    r["last"], thr, r["count"], r["flags"], slots)
+        return ex
 
     def percentiles(self, resource: ResourceType, percentiles: Sequence, mode: str = "ref_index",
                     return_flags: bool = False):

@@ -335,6 +335,39 @@ class SimpleEngine:
         host["flags"] = host["flags"].view(np.uint32)
         return host
 
+    def exceed_series(self, ps: PackedSeries, thresholds) -> dict:
+        """Per segment and threshold, the samples above it (krr_segmented_exceed): host arrays
+        ``above``, ``longest``, ``head``, ``tail``, ``last`` (int64) and ``excess`` (float64),
+        [R, S] each, row r for ``thresholds[r]``; ``count`` (int64) and ``flags`` (uint32), [S].
+        ``thresholds`` is float64 [R, S] with any R >= 1: rows run in groups of
+        KRR_MAX_THRESHOLDS, each group one pass over the series (a host chunk is uploaded once
+        and serves all its groups).  Chunks and synchronisation as ``stats_series``; a chunk
+        takes the thresholds of its own segment range."""
+        import torch
+
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if thr.ndim != 2 or thr.shape[0] < 1 or thr.shape[1] != ps.n_segments:
+            raise ValueError(f"thresholds must be float64 [R, {ps.n_segments}] with R >= 1, got shape {thr.shape}")
+        ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        R, G = thr.shape[0], _native.KRR_MAX_THRESHOLDS
+        ints = ("above", "longest", "head", "tail", "last")
+        parts, lo = [], 0
+        for part in self._series_parts(ps):
+            hi = lo + part.n_segments
+            if R > G:
+                part = self._resident(part)
+            groups = [self._exceed_part(ctx, part, thr[a:a + G, lo:hi]) for a in range(0, R, G)]
+            out = groups[0]
+            if len(groups) > 1:  # rows of the groups one under the other; count and flags are the same in each
+                out = {**out, **{k: torch.cat([g[k] for g in groups], dim=0) for k in ints + ("excess",)}}
+            parts.append(out)
+            lo = hi
+        host = self._host_concat(parts, {**{k: np.int64 for k in ints}, "excess": np.float64,
+                                         "count": np.int64, "flags": np.int32},
+                                 rows={**{k: R for k in ints}, "excess": R})
+        host["flags"] = host["flags"].view(np.uint32)
+        return host
+
     def percentiles_series(self, ps: PackedSeries, params_list) -> tuple:
         """Several percentiles of every segment of one series — CPU or memory — through
         krr_segmented_percentiles: (value float64 [P, S], count int64 [S], flags uint32 [P, S]),
@@ -407,6 +440,32 @@ class SimpleEngine:
             ctx.segmented_moments(series, out["mean"], out["m2"], out.get("tmean"), out.get("t2"), out.get("cxt"),
                                   out["count"], out["flags"])
         return out
+
+    def _exceed_part(self, ctx, part: PackedSeries, thresholds: np.ndarray) -> dict:
+        """Upload (host series, and the chunk's thresholds [R, n], R <= KRR_MAX_THRESHOLDS) and
+        one krr_segmented_exceed launch on the current stream: the six outputs [R, n] and the
+        count / flags [n] as device tensors."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        R, n = thresholds.shape
+        with torch.cuda.device(self.device):
+            series = self._part_series(ctx, part)
+            thr = torch.from_numpy(np.ascontiguousarray(thresholds, dtype=np.float64)).to(dev)
+            out = {k: torch.empty((R, n), dtype=torch.int64, device=dev)
+                   for k in ("above", "longest", "head", "tail", "last")}
+            out["excess"] = torch.empty((R, n), dtype=torch.float64, device=dev)
+            out["count"] = torch.empty(n, dtype=torch.int64, device=dev)
+            out["flags"] = torch.empty(n, dtype=torch.int32, device=dev)
+            ctx.segmented_exceed(series, thr, R, out["above"], out["excess"], out["longest"], out["head"],
+                                 out["tail"], out["last"], out["count"], out["flags"])
+        return out
+
+    def _resident(self, part: PackedSeries) -> PackedSeries:
+        """The chunk with its values and offsets in HBM (as it is when it is there already), for
+        several launches over one upload."""
+        vals, offs = self._to_device(part)
+        return PackedSeries(vals, offs, int(part.max_len), part.gaps_are_nan)
 
     def _percentiles_part(self, ctx, part: PackedSeries, params_list: list) -> dict:
         """Upload (host series) and krr_segmented_percentiles per group of KRR_MAX_PERCENTILES

@@ -3456,6 +3456,227 @@ __global__ __launch_bounds__(64) void k_moments(MomentsArgs A) {
     }
 }
 
+// ------------------------------ EXCEED -------------------------------------
+// krr_segmented_exceed: per segment and threshold tau, how many present samples are above tau
+// (x > tau, strict), by how much in sum, and the run structure: longest run, the run at the
+// segment's start (head), the run at its end (tail) and the slot of the last sample above.
+// Absent slots (gaps, padding) are transparent: they neither count nor end a run.
+//
+// Run statistics of a slot sequence are the tuple (n present, a above, h, t, b); two adjacent
+// sequences merge associatively (run_merge), the empty tuple is the identity.  The skeleton
+// hands a chunk over as kUnroll unit rows: in row u lanes 0..63 hold 128 consecutive slots, lane
+// l's .x is slot 2l and .y slot 2l + 1 of the row, rows and chunks in slot order; in the partial
+// last chunk lane 63 of the last row holds the segment's unaligned head (slot 0) in .x and its
+// unaligned tail (slot L - 1) in .y instead of body slots.  A row's tuple comes from four
+// ballots (present / above of .x and of .y).  Nothing above: only n moves, and t drops to 0 when
+// a present slot was seen.  No breaker (a present slot that is not above): the row is one run.
+// Otherwise n and a are popcounts, h and t are popcounts of the above masks before the first and
+// after the last breaker (scalar), and for b every lane counts, from the masks alone, the slots
+// above since the last breaker before its own two slots, adds those, and the wave takes the
+// maximum: no tuple scan, and the same cost whether the row holds one run or sixty-four.  The
+// row's tuple merges into a wave-uniform running tuple of the body; head slot, body and tail
+// slot are merged in that order at the end, whatever order they arrived in.
+// The excess is summed per lane in meeting order and folded like k_stats' sum: one rounded
+// subtraction per term, terms >= 0, no atomics — the same buffers give the same bits on every
+// launch, and threshold r runs the same arithmetic whatever R is (contraction is off).
+struct RunTuple {
+    uint32_t n, a, h, t, b;  // present, above, head run, tail run, longest run (segments < 2^32 slots, as k_stats)
+};
+__device__ __forceinline__ RunTuple run_merge(const RunTuple& x, const RunTuple& y) {  // x's slots, then y's
+    RunTuple r;
+    r.n = x.n + y.n;
+    r.a = x.a + y.a;
+    r.h = x.h == x.n ? x.n + y.h : x.h;
+    r.t = y.t == y.n ? y.n + x.t : y.t;
+    const uint32_t m = x.b > y.b ? x.b : y.b, j = x.t + y.h;
+    r.b = m > j ? m : j;
+    return r;
+}
+
+struct OpMaxU32 {
+    __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return b > a ? b : a; }
+};
+
+template <int R>
+struct ExceedProc {
+    double tau[R];
+    double ex[R];        // per lane: sum of (x - tau) over the slots above that the lane met
+    RunTuple body[R];    // wave-uniform: the body rows so far
+    uint32_t last[R];    // wave-uniform: last body slot above (meaningful once body[r].a > 0)
+    uint32_t present;    // wave-uniform: non-NaN slots so far, head and tail slot included
+    uint32_t base;       // slot index of lane 0's .x in the row to come
+    uint32_t full;       // full chunks still to come before the partial one
+    uint32_t head_p, tail_p;  // the unaligned head / tail slot is present
+    uint32_t head_a, tail_a;  // ... and above threshold r: bit r
+    uint64_t below, upto;     // per lane: the lanes before this one, and with it
+    bool last_lane;
+    __device__ __forceinline__ ExceedProc(int64_t beg, int64_t end, int lane) {
+        below = (1ull << lane) - 1;
+        upto = below | 1ull << lane;
+        int64_t a0 = (beg + 1) & ~(int64_t)1;
+        if (a0 > end) a0 = end;
+        int64_t a1 = end & ~(int64_t)1;
+        if (a1 < a0) a1 = a0;
+        full = (uint32_t)(((a1 >> 1) - (a0 >> 1)) / (kUnroll * kWave));
+        base = (uint32_t)(a0 - beg);
+        present = 0;
+        head_p = tail_p = head_a = tail_a = 0u;
+        last_lane = lane == kWave - 1;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            ex[r] = 0.0;
+            body[r] = RunTuple{0, 0, 0, 0, 0};
+            last[r] = 0;
+        }
+    }
+    __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
+        const bool partial = full == 0;  // wave-uniform
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const double x = c[u].x, y = c[u].y;
+            uint64_t px = ballot(!__builtin_isnan(x)), py = ballot(!__builtin_isnan(y));
+            present += popc64(px) + popc64(py);
+            // lane 63 of a partial chunk's last row: the head and tail slot, not body slots
+            const bool edge = u == kUnroll - 1 && partial;
+            const uint64_t keep = edge ? ~0ull >> 1 : ~0ull;
+            if (edge) {
+                head_p = (uint32_t)(px >> 63);
+                tail_p = (uint32_t)(py >> 63);
+            }
+            px &= keep;
+            py &= keep;
+            const uint32_t nr = popc64(px) + popc64(py);
+            const bool live = !(edge && last_lane);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const bool gx = x > tau[r], gy = y > tau[r];
+                ex[r] += gx ? x - tau[r] : 0.0;
+                ex[r] += gy ? y - tau[r] : 0.0;
+                uint64_t ax = ballot(gx), ay = ballot(gy);
+                if (edge) {
+                    head_a |= (uint32_t)(ax >> 63) << r;
+                    tail_a |= (uint32_t)(ay >> 63) << r;
+                }
+                ax &= keep;
+                ay &= keep;
+                RunTuple& B = body[r];
+                if ((ax | ay) == 0) {
+                    if (nr) B.t = 0;
+                    B.n += nr;
+                    continue;
+                }
+                const uint32_t ar = popc64(ax) + popc64(ay);
+                RunTuple row{nr, ar, ar, ar, ar};
+                if (ar != nr) {
+                    // breakers: present and not above.  The row is slots (lane 0 .x, lane 0 .y, lane 1 .x, ...)
+                    const uint64_t bx = px & ~ax, by = py & ~ay;
+                    // head: the slots above before the first breaker; tail: those after the last one
+                    const int fx = bx ? __builtin_ctzll(bx) : 64, fy = by ? __builtin_ctzll(by) : 64;
+                    const int lx = bx ? 63 - __clzll((long long)bx) : -1, ly = by ? 63 - __clzll((long long)by) : -1;
+                    if (fx <= fy) {  // .x of lane fx: the lanes below it, both slots
+                        const uint64_t m = (1ull << fx) - 1;
+                        row.h = popc64(ax & m) + popc64(ay & m);
+                    } else {  // .y of lane fy: its own .x too
+                        const uint64_t m = (1ull << fy) - 1;
+                        row.h = popc64(ax & (m | 1ull << fy)) + popc64(ay & m);
+                    }
+                    if (ly >= lx) {  // .y of lane ly: the lanes above it, both slots
+                        const uint64_t m = (~0ull << ly) << 1;
+                        row.t = popc64(ax & m) + popc64(ay & m);
+                    } else {  // .x of lane lx: its own .y too
+                        const uint64_t m = ~0ull << lx;
+                        row.t = popc64(ax & (m << 1)) + popc64(ay & m);
+                    }
+                    // longest: the runs between the row's first and last breaker hold ar - h - t slots
+                    // together.  While the body's longest run so far is at least that, none of them
+                    // can change the answer and max(h, t) stands in for the row's longest run (h and
+                    // t still act across the rows through t + h).  Else every lane counts the slots
+                    // above between the last breaker before its .x (in lane J = jp - 1; none: jp = 0)
+                    // and its .x: those of lanes J + 1 .. l - 1, and lane J's .y when that is above
+                    // (ay << 1 puts it on bit J + 1 = jp).  From there the lane's own two slots give the
+                    // run that ends at each; the row's longest run is the largest of them.
+                    row.b = row.h > row.t ? row.h : row.t;
+                    if (ar - row.h - row.t > B.b) {
+                        const uint64_t brk = (bx | by) & below;
+                        const uint32_t bh = (uint32_t)(brk >> 32), bl = (uint32_t)brk;
+                        const int jp = bh ? 64 - __clz((int)bh) : bl ? 32 - __clz((int)bl) : 0;  // <= 63: lanes < l
+                        const uint64_t from = ~0ull << jp;
+                        const uint32_t cx = popc64(ax & below & from) + popc64((ay << 1) & upto & from);
+                        const bool xa = gx && live, xb = !__builtin_isnan(x) && !gx && live, ya = gy && live;
+                        const uint32_t cy = xb ? 0u : cx + (xa ? 1u : 0u);
+                        const uint32_t best = ya ? cy + 1u : xa ? cx + 1u : 0u;
+                        row.b = lane_bcast32(wave_scan32(best, 0u, OpMaxU32{}), kWave - 1);
+                    }
+                }
+                B = run_merge(B, row);
+                const int hx = ax ? 2 * (63 - __clzll((long long)ax)) : -1;
+                const int hy = ay ? 2 * (63 - __clzll((long long)ay)) + 1 : -1;
+                last[r] = base + (uint32_t)(hx > hy ? hx : hy);
+            }
+            base += 2 * kWave;
+        }
+        --full;
+    }
+};
+
+struct ExceedArgs {
+    const double* vals;
+    const int64_t* offs;
+    int64_t S;
+    int32_t gaps;
+    int32_t remap;      // xcd_item, chosen as max_args chooses it
+    const double* thr;  // [R * S], row-major
+    int64_t* out_above;    // the six [R * S] outputs may each be null
+    double* out_excess;
+    int64_t* out_longest;
+    int64_t* out_head;
+    int64_t* out_tail;
+    int64_t* out_last;
+    int64_t* out_n;
+    uint32_t* out_f;
+};
+
+// The body holds kUnroll x R row steps, so it takes the skeleton's single-site loop (one inlined
+// chunk body), as k_moments<true> does; the chunks arrive in the same order either way.
+template <int R>
+__global__ __launch_bounds__(64) void k_exceed(ExceedArgs A) {
+    const int lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < A.S; b += gridDim.x) {
+        const int64_t s = xcd_item(b, A.S, A.remap);
+        const int64_t beg = A.offs[s], end = A.offs[s + 1];
+        ExceedProc<R> P(beg, end, lane);
+#pragma unroll
+        for (int r = 0; r < R; ++r) P.tau[r] = A.thr[(int64_t)r * A.S + s];
+        stream_segment<true>(A.vals, beg, end, P, lane);
+        const uint64_t L = (uint64_t)(end - beg);
+        const uint64_t n = A.gaps ? P.present : L;  // padding is NaN: present counts real slots only
+        uint32_t flags = 0;
+        if (n == 0) flags = KRR_FLAG_EMPTY;
+        else if (P.present != L && !A.gaps) flags = KRR_FLAG_NAN;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const double ex = wave_sum_f64(P.ex[r]);
+            const uint32_t ha = (P.head_a >> r) & 1u, ta = (P.tail_a >> r) & 1u;
+            const RunTuple head{P.head_p, ha, ha, ha, ha}, tail{P.tail_p, ta, ta, ta, ta};
+            const RunTuple t = run_merge(run_merge(head, P.body[r]), tail);
+            const int64_t last = ta ? (int64_t)L - 1 : P.body[r].a ? (int64_t)P.last[r] : ha ? 0 : -1;
+            if (lane == 0) {
+                const int64_t o = (int64_t)r * A.S + s;
+                if (A.out_above) A.out_above[o] = flags ? 0 : (int64_t)t.a;
+                if (A.out_excess) A.out_excess[o] = flags & KRR_FLAG_NAN ? bitsd(kQuietNaN) : flags ? 0.0 : ex;
+                if (A.out_longest) A.out_longest[o] = flags ? 0 : (int64_t)t.b;
+                if (A.out_head) A.out_head[o] = flags ? 0 : (int64_t)t.h;
+                if (A.out_tail) A.out_tail[o] = flags ? 0 : (int64_t)t.t;
+                if (A.out_last) A.out_last[o] = flags ? -1 : last;
+            }
+        }
+        if (lane == 0) {
+            A.out_n[s] = (int64_t)n;
+            A.out_f[s] = flags;
+        }
+    }
+}
+
 }  // namespace krr
 #include "krr_kll.h"
 namespace krr {
@@ -4210,6 +4431,38 @@ int krr_segmented_moments(krr_ctx* ctx, const krr_series* series, double* out_me
                         out_m2,         out_tmean,       out_t2, out_cxt,              out_count, out_flags};
     if (n_trend) hipLaunchKernelGGL(k_moments<true>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
     else hipLaunchKernelGGL(k_moments<false>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
+    KRR_HIP(ctx, hipGetLastError());
+    return KRR_OK;
+}
+
+int krr_segmented_exceed(krr_ctx* ctx, const krr_series* series, const double* thresholds, int32_t n_thresholds,
+                         int64_t* out_above, double* out_excess, int64_t* out_longest, int64_t* out_head,
+                         int64_t* out_tail, int64_t* out_last, int64_t* out_count, uint32_t* out_flags,
+                         void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    int rc = check_series(ctx, series);
+    if (rc) return rc;
+    const int64_t S = series->n_segments;
+    if (S == 0) return KRR_OK;
+    if (n_thresholds < 1 || n_thresholds > KRR_MAX_THRESHOLDS)
+        return set_err(ctx, KRR_E_INVALID, "n_thresholds outside 1..KRR_MAX_THRESHOLDS%s: %lld", "", (long long)n_thresholds);
+    if (!thresholds || !out_count || !out_flags)
+        return set_err(ctx, KRR_E_INVALID, "null thresholds or outputs%s", "");
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    const MaxArgs M = max_args(series, nullptr, out_count, out_flags, nullptr);  // its remap choice
+    const ExceedArgs A{series->values, series->offsets, S,          series->gaps_are_nan, M.remap,
+                       thresholds,     out_above,       out_excess, out_longest,          out_head,
+                       out_tail,       out_last,        out_count,  out_flags};
+    const dim3 grid(grid_for(S)), block(64);
+    const hipStream_t st = (hipStream_t)stream;
+    static_assert(KRR_MAX_THRESHOLDS == 4, "one k_exceed instantiation per threshold count");
+    switch (n_thresholds) {
+        case 1: hipLaunchKernelGGL(k_exceed<1>, grid, block, 0, st, A); break;
+        case 2: hipLaunchKernelGGL(k_exceed<2>, grid, block, 0, st, A); break;
+        case 3: hipLaunchKernelGGL(k_exceed<3>, grid, block, 0, st, A); break;
+        default: hipLaunchKernelGGL(k_exceed<4>, grid, block, 0, st, A); break;
+    }
     KRR_HIP(ctx, hipGetLastError());
     return KRR_OK;
 }
