@@ -246,6 +246,46 @@ int krr_segmented_exceed(krr_ctx* ctx, const krr_series* series, const double* t
                          int64_t* out_longest, int64_t* out_head, int64_t* out_tail, int64_t* out_last,
                          int64_t* out_count, uint32_t* out_flags, void* stream);
 
+/* Per segment, ONE pass: the series cut into windows of `window` slots, with count, min, max and
+ * sum per window — the coarser time axis (5-minute means, hourly peaks; krr_amd.api.FleetRollup).
+ * For segment s with L = offsets[s+1] - offsets[s] slots and W = window:
+ *   - nw = ceil(L / W) windows, none when L == 0;
+ *   - slot i belongs to window (i + ph) / W, with ph = 0 for KRR_ROLLUP_START (window w covers
+ *     slots [w W, (w+1) W): the LAST window may be partial) and ph = (W - L % W) % W for
+ *     KRR_ROLLUP_END (the windows end at the series' last slot: the FIRST window may be partial);
+ *   - window w is written at index win_offsets[s] + w of each per-window output.
+ * win_offsets (device, [n_segments + 1]) comes from the caller: the exclusive cumulative sum of nw,
+ *   win_offsets[0] = 0, win_offsets[s+1] = win_offsets[s] + (L_s + W - 1) / W,
+ * or any layout that leaves every segment at least nw entries.  The kernel derives nw itself: where
+ * win_offsets[s+1] - win_offsets[s] < nw it writes NO window of that segment and sets
+ * KRR_FLAG_CAPACITY on it; it never writes outside [win_offsets[s], win_offsets[s] + nw).
+ * Per window, P = its present slots: every slot, or the non-NaN slots when gaps_are_nan.
+ *   wcount = |P|
+ *   wmin, wmax = an extremal sample's own bits under float comparison, an extremum of zero as
+ *             +0.0 (deterministic without a second pass); the quiet NaN 0x7FF8000000000000 when P
+ *             is empty — as a value of a gapped series that is an absent slot
+ *   wsum    = a plain IEEE float64 sum of P in one fixed order, uncompensated, +0.0 when P is
+ *             empty: within (m-1) u / (1 - (m-1) u) x sum|x| of the exact sum, m = wcount,
+ *             u = 2^-53 (any order of m - 1 additions, as for krr_segmented_stats' sum).  The same
+ *             buffers give the same bits on every launch (no atomics); the order may depend on the
+ *             parity of the segment's start offset; no output's bits depend on which others are NULL
+ *   - a window that holds a NaN sample in the compact layout (gaps_are_nan == 0): wmin = wmax =
+ *     wsum = the quiet NaN, wcount = the window's slot count.  NaN propagates per window;
+ *   - +-Inf: plain IEEE, no flag.
+ * Each of the four per-window outputs may be NULL and is then not written.
+ * out_count, out_flags ([n_segments]): bit-identical to krr_segmented_stats on the same series,
+ * plus KRR_FLAG_CAPACITY as above.
+ * KRR_E_INVALID: a null ctx or series; window outside 1 .. 2^31-1; align neither value;
+ * win_offsets, out_count or out_flags NULL while n_segments > 0.  n_segments == 0 launches nothing.
+ * One wave per segment, one read of every value; no atomics, no LDS.  Segments of fewer than 2^32
+ * slots, as krr_segmented_stats. */
+#define KRR_ROLLUP_START 0
+#define KRR_ROLLUP_END 1
+int krr_segmented_rollup(krr_ctx* ctx, const krr_series* series, int64_t window, int32_t align,
+                         const int64_t* win_offsets, double* out_wmin, double* out_wmax,
+                         double* out_wsum, uint32_t* out_wcount, int64_t* out_count,
+                         uint32_t* out_flags, void* stream);
+
 /* SimpleStrategy.run over every object: cpu and mem each hold one segment per
  * object (same n_segments).  Outputs are device pointers of n_segments entries. */
 int krr_simple_run(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,

@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "krr_segmented_stats",
     "krr_segmented_moments",
     "krr_segmented_exceed",
+    "krr_segmented_rollup",
     "krr_simple_run",
     "krr_simple_run_records",
     "krr_simple_run_forward",
@@ -235,6 +236,8 @@ class KrrSelectPlanInfo(ctypes.Structure):
 
 KRR_MAX_PERCENTILES = 4
 KRR_MAX_THRESHOLDS = 4  # krr_segmented_exceed: thresholds per launch
+KRR_ROLLUP_START = 0  # krr_segmented_rollup: windows start with the series (the last may be partial)
+KRR_ROLLUP_END = 1    # ... or end with it (the first may be partial)
 
 
 class KrrMultiPlanInfo(ctypes.Structure):
@@ -301,6 +304,8 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_segmented_moments.restype = ctypes.c_int
         lib.krr_segmented_exceed.argtypes = [vp, sp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_segmented_exceed.restype = ctypes.c_int
+        lib.krr_segmented_rollup.argtypes = [vp, sp, i64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_segmented_rollup.restype = ctypes.c_int
         lib.krr_simple_run.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.restype = ctypes.c_int
@@ -547,6 +552,27 @@ class Context:
         self._check(self._lib.krr_segmented_exceed(
             self._h, ctypes.byref(series), thresholds.data_ptr(), n_thresholds,
             *(None if t is None else t.data_ptr() for t in (above, excess, longest, head, tail, last)),
+            count.data_ptr(), flags.data_ptr(), self._stream(stream)))
+
+    def segmented_rollup(self, series: KrrSeries, window: int, align: int, win_offsets, wmin, wmax, wsum, wcount,
+                         count, flags, stream=None) -> None:
+        """Count, min, max and sum of every window of ``window`` slots of every segment, from one
+        pass (krr_segmented_rollup).  ``align``: KRR_ROLLUP_START or KRR_ROLLUP_END.
+        ``win_offsets`` int64 [S + 1] says where each segment's windows go in the flat per-window
+        outputs ``wmin`` / ``wmax`` / ``wsum`` (float64) and ``wcount`` (int32 storage, read as
+        uint32), which must reach to the largest entry of win_offsets (the caller's business: the
+        kernel writes ceil(L / window) windows from win_offsets[s] and none where the span to
+        win_offsets[s + 1] is smaller); each is optional (None: not written).  ``count`` int64 [S]
+        and ``flags`` int32 [S] are required."""
+        _check_tensor(win_offsets, "int64", series.n_segments + 1)
+        for t, dt in ((wmin, "float64"), (wmax, "float64"), (wsum, "float64"), (wcount, "int32")):
+            if t is not None:
+                _check_tensor(t, dt)
+        _check_tensor(count, "int64", series.n_segments)
+        _check_tensor(flags, "int32", series.n_segments)
+        self._check(self._lib.krr_segmented_rollup(
+            self._h, ctypes.byref(series), int(window), int(align), win_offsets.data_ptr(),
+            *(None if t is None else t.data_ptr() for t in (wmin, wmax, wsum, wcount)),
             count.data_ptr(), flags.data_ptr(), self._stream(stream)))
 
     def simple_run(self, cpu: KrrSeries, mem: KrrSeries, params: KrrPercentileParams, out: dict,

@@ -42,7 +42,8 @@ from krr_amd.core.models.allocations import ResourceType
 from krr_amd.core.packing import PackedFleet, PackedSeries, pack_resource, pod_view
 from krr_amd.utils.prom_decimal import prom_decimal
 
-__all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetStats", "allocation_thresholds"]
+__all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetProfile", "FleetRollup", "FleetStats",
+           "allocation_thresholds"]
 
 
 @dataclass
@@ -251,6 +252,211 @@ class FleetExceedance:
                                self.thresholds, na + nb, flags, self.slots + other.slots)
 
 
+_ROLLUP_ALIGN = {"start": _native.KRR_ROLLUP_START, "end": _native.KRR_ROLLUP_END}
+_ROLLUP_SERIES_STATS = ("min", "max", "sum", "mean")
+_ROLLUP_STATS = ("wcount",) + _ROLLUP_SERIES_STATS
+
+
+@dataclass
+class FleetProfile:
+    """``FleetRollup.fold(period)``: per object and position mod ``period`` the windows combined
+    (host arrays [S, period]).  ``count`` is the present samples, ``min`` / ``max`` NaN and ``sum``
+    0 where ``count`` is 0; a column that took a NaN window (a NaN sample in the compact layout)
+    is NaN in ``min``, ``max`` and ``sum``."""
+    count: np.ndarray  # int64 [S, period]
+    min: np.ndarray    # float64
+    max: np.ndarray    # float64
+    sum: np.ndarray    # float64
+
+    @property
+    def mean(self) -> np.ndarray:
+        """sum / count in float64; NaN where count == 0."""
+        out = np.full(self.count.shape, np.nan, dtype=np.float64)
+        np.divide(self.sum, self.count, out=out, where=self.count > 0)
+        return out
+
+
+class FleetRollup:
+    """One resource of a fleet with the time axis coarsened: every object's series cut into
+    windows of ``window`` slots, and per window the count, min, max and sum of its present samples
+    (one krr_segmented_rollup pass; include/krr_amd.h has the rules).  ``align="end"``: the windows
+    end at each series' last slot and the FIRST may be partial — fleets end "now", so windows of
+    series of different length line up in wall-clock time; ``"start"``: they start at slot 0 and
+    the LAST may be partial.
+
+    Object s owns windows ``offsets[s] .. offsets[s+1]`` of the flat per-window arrays (``offsets``
+    int64 [S + 1], ``n_windows`` [S], ``slots`` [S] the series' lengths, all host).  The per-window
+    arrays live in HBM; ``wcount``, ``min``, ``max``, ``sum`` and ``mean`` (sum / wcount computed
+    there, NaN where wcount == 0) copy them to the host on first use.  A window without a present
+    sample has wcount 0, min = max = NaN, sum 0.  ``count`` and ``flags`` ([S], host) are
+    ``FleetBatch.stats``' for the whole series.
+
+    Two rollups of adjacent time slices cannot be merged: a window that straddles the cut would
+    need both sides' partial windows, which the window grid of either side does not keep.  There
+    is no ``concat``; roll up the joined series instead."""
+
+    def __init__(self, resource, window: int, align: str, offsets, slots, count, flags, wcount, wmin, wmax, wsum,
+                 device: int = 0, engine: Optional[SimpleEngine] = None):
+        import torch
+
+        self.resource = ResourceType(resource)
+        self.window = int(window)
+        self.align = str(align)
+        if self.align not in _ROLLUP_ALIGN:
+            raise ValueError(f"unknown align {align!r}; expected 'start' or 'end'")
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        self.slots = np.asarray(slots, dtype=np.int64)
+        self.count = np.asarray(count, dtype=np.int64)
+        self.flags = np.asarray(flags).astype(np.uint32)
+        self.device = int(device)
+        self._engine = engine
+        self._t = {"wcount": torch.as_tensor(wcount), "min": torch.as_tensor(wmin), "max": torch.as_tensor(wmax),
+                   "sum": torch.as_tensor(wsum)}
+        n = int(self.offsets[-1]) if self.offsets.size else 0
+        if self.offsets.size != self.slots.size + 1 or any(t.numel() != n for t in self._t.values()):
+            raise ValueError("offsets, slots and the per-window arrays do not describe the same windows")
+        self._host: dict = {}
+        self._batches: dict = {}
+
+    @property
+    def n_objects(self) -> int:
+        return self.slots.size
+
+    @property
+    def n_windows(self) -> np.ndarray:
+        return np.diff(self.offsets)
+
+    @staticmethod
+    def _stat(stat: str, allowed=_ROLLUP_STATS) -> str:
+        if stat not in allowed:
+            raise ValueError(f"unknown stat {stat!r}; expected one of {list(allowed)}")
+        return stat
+
+    def tensor(self, stat: str):
+        """The flat per-window tensor of ``stat`` where the kernel left it (HBM): ``wcount`` int32,
+        the others float64."""
+        import torch
+
+        stat = self._stat(stat)
+        t = self._t.get(stat)
+        if t is None:  # mean
+            n = self._t["wcount"]
+            t = self._t["mean"] = torch.where(n > 0, self._t["sum"] / n.to(torch.float64),
+                                              torch.full_like(self._t["sum"], float("nan")))
+        return t
+
+    def _flat(self, stat: str) -> np.ndarray:
+        a = self._host.get(stat)
+        if a is None:
+            a = self._host[stat] = self.tensor(stat).cpu().numpy()
+        return a
+
+    wcount = property(lambda self: self._flat("wcount"), doc="present samples per window (int32, flat, host)")
+    min = property(lambda self: self._flat("min"), doc="float64, flat, host")
+    max = property(lambda self: self._flat("max"), doc="float64, flat, host")
+    sum = property(lambda self: self._flat("sum"), doc="float64, flat, host")
+    mean = property(lambda self: self._flat("mean"), doc="sum / wcount, NaN where wcount == 0 (float64, flat, host)")
+
+    def of(self, s: int, stat: str = "mean") -> np.ndarray:
+        """The windows of object ``s``, oldest first."""
+        s = int(s)
+        if not 0 <= s < self.n_objects:
+            raise IndexError(f"object {s} of {self.n_objects}")
+        return self._flat(stat)[self.offsets[s]:self.offsets[s + 1]]
+
+    def _dense_index(self, width: int):
+        """(rows, columns) of every window in a [S, width] layout: right-justified for
+        ``align="end"`` (the last column is every series' last window), else left-justified."""
+        nw = self.n_windows
+        rows = np.repeat(np.arange(self.n_objects, dtype=np.int64), nw)
+        cols = np.arange(int(self.offsets[-1]), dtype=np.int64) - np.repeat(self.offsets[:-1], nw)
+        if self.align == "end":
+            cols += np.repeat(width - nw, nw)
+        return rows, cols
+
+    def dense(self, stat: str = "mean") -> np.ndarray:
+        """float64 [S, max windows], NaN where an object has no window: right-justified for
+        ``align="end"``, left-justified for ``"start"``."""
+        flat = self._flat(stat)
+        width = int(self.n_windows.max()) if self.n_objects else 0
+        out = np.full((self.n_objects, width), np.nan, dtype=np.float64)
+        rows, cols = self._dense_index(width)
+        out[rows, cols] = flat
+        return out
+
+    def as_batch(self, stat: str = "mean") -> "FleetBatch":
+        """A FleetBatch whose series of this resource is the per-window ``stat`` (``min``, ``max``,
+        ``sum`` or ``mean``), in HBM as it is: a gapped series over the window offsets, a window
+        without a present sample being an absent slot.  ``stats``, ``moments``, ``exceedance``,
+        ``percentiles`` and a further ``rollup`` apply to it.  Raises ValueError if an object is
+        flagged KRR_FLAG_NAN: its NaN windows would read as absent and the NaN be dropped."""
+        import torch
+
+        stat = self._stat(stat, _ROLLUP_SERIES_STATS)
+        if (self.flags & _native.KRR_FLAG_NAN).any():
+            s = int(np.flatnonzero(self.flags & _native.KRR_FLAG_NAN)[0])
+            raise ValueError(f"object {s} holds a NaN sample (KRR_FLAG_NAN): as a gapped series its NaN windows "
+                             f"would be dropped silently")
+        batch = self._batches.get(stat)
+        if batch is None:
+            vals = self.tensor(stat)
+            if stat == "sum":
+                vals = torch.where(self._t["wcount"] > 0, vals, torch.full_like(vals, float("nan")))
+            longest = int(self.n_windows.max()) if self.n_objects else 0
+            if vals.is_cuda:
+                ps = PackedSeries(vals.contiguous(), torch.from_numpy(self.offsets).to(vals.device), longest, True)
+            else:
+                ps = PackedSeries(vals.numpy(), self.offsets, longest, True)
+            batch = self._batches[stat] = FleetBatch._of({self.resource: ps}, self.n_objects, self.device,
+                                                         self._engine)
+        return batch
+
+    def peak(self, stat: str = "mean") -> np.ndarray:
+        """float64 [S]: the largest window value of every object — with ``mean`` the sustained
+        peak (the highest ``window``-slot average); NaN without a present sample."""
+        return self.as_batch(stat).stats(self.resource).max
+
+    def fold(self, period: int) -> FleetProfile:
+        """The windows whose position is congruent mod ``period`` combined, per object: column
+        ``period - 1`` holds each series' last window for ``align="end"``, column 0 its first for
+        ``"start"``.  With ``window=60`` on a 1-minute step and ``period=24`` this is the
+        hour-of-day profile.  Computed where the per-window tensors live; sums add in one fixed
+        order (oldest window first)."""
+        import torch
+
+        if isinstance(period, bool) or not isinstance(period, (int, np.integer)) or period < 1:
+            raise ValueError(f"period must be an int >= 1, got {period!r}")
+        period, S = int(period), self.n_objects
+        nwmax = int(self.n_windows.max()) if S else 0
+        reps = max(-(-nwmax // period), 1)
+        width = reps * period
+        rows, cols = self._dense_index(width)
+        wc = self._t["wcount"]
+        idx = torch.from_numpy(rows * width + cols).to(wc.device)
+        inf = float("inf")
+
+        def grid(src, fill):
+            g = torch.full((S * width,), fill, dtype=src.dtype, device=wc.device)
+            g[idx] = src
+            return g.view(S, reps, period)
+
+        absent = wc <= 0
+        bad = grid((~absent & torch.isnan(self._t["sum"])).to(torch.int32), 0).sum(dim=1) > 0
+        count = grid(wc.to(torch.int64), 0).sum(dim=1)
+        nan = torch.full((S, period), float("nan"), dtype=torch.float64, device=wc.device)
+        mn = grid(torch.where(absent, torch.full_like(self._t["min"], inf), self._t["min"]), inf).amin(dim=1)
+        mx = grid(torch.where(absent, torch.full_like(self._t["max"], -inf), self._t["max"]), -inf).amax(dim=1)
+        sm = grid(self._t["sum"], 0.0)
+        total = sm[:, 0, :].clone()
+        for r in range(1, reps):
+            total += sm[:, r, :]
+        none = count == 0
+        mn = torch.where(none | bad, nan, mn)
+        mx = torch.where(none | bad, nan, mx)
+        total = torch.where(bad, nan, total)
+        return FleetProfile(count.cpu().numpy(), mn.cpu().numpy(), mx.cpu().numpy(), total.cpu().numpy())
+
+
 def allocation_thresholds(objects: Sequence, resource: ResourceType, which: str = "requests") -> np.ndarray:
     """float64 [S]: each object's current request (or, ``which="limits"``, limit) of ``resource``
     from ``K8sObjectData.allocations``, as a threshold row for ``FleetBatch.exceedance``.  An
@@ -392,6 +598,39 @@ class FleetBatch:
             ex = self._cache[key] = FleetExceedance(r["above"], r["excess"], r["longest"], r["head"], r["tail"],
                                                     r["last"], thr, r["count"], r["flags"], slots)
         return ex
+
+    def rollup(self, resource: ResourceType, window: int, align: str = "end") -> FleetRollup:
+        """Every object's series cut into windows of ``window`` slots, with count, min, max and sum
+        per window (FleetRollup): one krr_segmented_rollup pass, cached per (resource, window,
+        align).  ``align="end"`` (the default) ends the windows at each series' last slot;
+        ``"start"`` starts them at its first.  The result's ``as_batch(stat)`` is a FleetBatch
+        again, so a percentile of smoothed usage is
+
+            batch.rollup(ResourceType.CPU, 5).as_batch("mean").percentile(ResourceType.CPU, "95", mode="linear")
+
+        and ``peak()`` the highest window mean.  Works on a ``per_pod()`` view unchanged (windows
+        per pod)."""
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= window <= 2**31 - 1:
+            raise ValueError(f"window must be an int in 1 .. 2^31-1 (slots), got {window!r}")
+        if align not in _ROLLUP_ALIGN:
+            raise ValueError(f"unknown align {align!r}; expected 'start' or 'end'")
+        resource = ResourceType(resource)
+        key = (resource, "rollup", int(window), align)
+        ru = self._cache.get(key)
+        if ru is None:
+            ps = self.series(resource)
+            r = self.engine.rollup_series(ps, int(window), _ROLLUP_ALIGN[align])
+            if (r["flags"] & _native.KRR_FLAG_CAPACITY).any():
+                s = int(np.flatnonzero(r["flags"] & _native.KRR_FLAG_CAPACITY)[0])
+                raise RuntimeError(f"object {s}: window offsets too small for its windows (KRR_FLAG_CAPACITY)")
+            offs = ps.offsets
+            if not isinstance(offs, np.ndarray) and hasattr(offs, "is_cuda"):
+                offs = offs.cpu().numpy()
+            slots = np.diff(np.asarray(offs, dtype=np.int64))
+            ru = self._cache[key] = FleetRollup(resource, int(window), align, r["offsets"], slots, r["count"],
+                                                r["flags"], r["wcount"], r["min"], r["max"], r["sum"],
+                                                self.device, self.engine)
+        return ru
 
     def percentiles(self, resource: ResourceType, percentiles: Sequence, mode: str = "ref_index",
                     return_flags: bool = False):

@@ -368,6 +368,68 @@ class SimpleEngine:
         host["flags"] = host["flags"].view(np.uint32)
         return host
 
+    def rollup_series(self, ps: PackedSeries, window: int, align: int) -> dict:
+        """Every segment of one series cut into windows of ``window`` slots
+        (krr_segmented_rollup; ``align`` KRR_ROLLUP_START or KRR_ROLLUP_END): ``wcount`` (int32),
+        ``min``, ``max``, ``sum`` (float64) as flat DEVICE tensors with one entry per window — at
+        a small window they are a large part of the series, so they stay in HBM — ``offsets``
+        (host int64 [S + 1]: segment s owns windows offsets[s] .. offsets[s+1]), ``count`` (int64)
+        and ``flags`` (uint32) as host arrays [S].  Chunks as ``stats_series``: the chunks'
+        windows are concatenated on the device and their offsets rebased.  The window offsets of
+        a host series come from its host offsets; for a series resident in HBM they are computed
+        there and read back, the one synchronisation before the outputs are sized."""
+        import torch
+
+        window = int(window)
+        ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        dev = torch.device("cuda", self.device)
+        parts, woffs, base = [], [np.zeros(1, dtype=np.int64)], 0
+        for part in self._series_parts(ps):
+            out, wo = self._rollup_part(ctx, part, window, align)
+            parts.append(out)
+            woffs.append(wo[1:] + base)
+            base += int(wo[-1])
+        names = (("wcount", torch.int32), ("min", torch.float64), ("max", torch.float64), ("sum", torch.float64))
+        if not parts:
+            res = {k: torch.empty(0, dtype=dt, device=dev) for k, dt in names}
+        elif len(parts) == 1:
+            res = {k: parts[0][k] for k, _ in names}
+        else:
+            res = {k: torch.cat([p[k] for p in parts]) for k, _ in names}
+        host = self._host_concat([{k: p[k] for k in ("count", "flags")} for p in parts],
+                                 {"count": np.int64, "flags": np.int32})
+        res.update(offsets=np.concatenate(woffs), count=host["count"], flags=host["flags"].view(np.uint32))
+        return res
+
+    def _rollup_part(self, ctx, part: PackedSeries, window: int, align: int) -> tuple:
+        """Upload (host series) and one krr_segmented_rollup launch on the current stream: the
+        chunk's device tensors and its window offsets as a host array."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(self.device):
+            series = self._part_series(ctx, part)
+            n = part.n_segments
+            if isinstance(part.offsets, np.ndarray):
+                wo = np.zeros(n + 1, dtype=np.int64)
+                np.cumsum(-(-np.diff(part.offsets.astype(np.int64, copy=False)) // window), out=wo[1:])
+                d_wo = torch.from_numpy(wo).to(dev)
+            else:
+                offs = series._keep[1]
+                d_wo = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+                torch.cumsum(torch.div(offs[1:] - offs[:-1] + (window - 1), window, rounding_mode="floor"), 0,
+                             out=d_wo[1:])
+                wo = d_wo.cpu().numpy()
+            nwin = int(wo[-1])
+            out = {"wcount": torch.empty(nwin, dtype=torch.int32, device=dev)}
+            for k in ("min", "max", "sum"):
+                out[k] = torch.empty(nwin, dtype=torch.float64, device=dev)
+            out["count"] = torch.empty(n, dtype=torch.int64, device=dev)
+            out["flags"] = torch.empty(n, dtype=torch.int32, device=dev)
+            ctx.segmented_rollup(series, window, align, d_wo, out["min"], out["max"], out["sum"], out["wcount"],
+                                 out["count"], out["flags"])
+        return out, wo
+
     def percentiles_series(self, ps: PackedSeries, params_list) -> tuple:
         """Several percentiles of every segment of one series — CPU or memory — through
         krr_segmented_percentiles: (value float64 [P, S], count int64 [S], flags uint32 [P, S]),

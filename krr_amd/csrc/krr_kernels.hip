@@ -3677,6 +3677,341 @@ __global__ __launch_bounds__(64) void k_exceed(ExceedArgs A) {
     }
 }
 
+// ------------------------------ ROLLUP -------------------------------------
+// krr_segmented_rollup: every segment cut into windows of W slots, count / min / max / sum per
+// window from ONE pass.  Slot i sits at position i + ph of the window grid (ph = 0 when the
+// windows start with the series, (W - L % W) % W when they end with it), window = position / W.
+// A row of the skeleton is 128 consecutive slots, lane l holding slots 2l (.x) and 2l + 1 (.y).
+//   - A row in which no window closes: every lane folds its two slots into its own partial of
+//     the open window, k_stats' branch-free body.  The common row once W >= 128.
+//   - A row in which windows close: the open window's partial is brought into lane 0 (one wave
+//     fold, only when lanes hold partials of earlier rows), each lane forms H = its .x when that
+//     is the last slot of its window, and A = its remaining slots, keyed by the window of .y;
+//     one segmented inclusive scan of A over the lanes (DPP, keys compared at every step: the
+//     keys do not decrease, so equal keys at distance d mean equal keys in between) gives every
+//     window's fold at the lane that holds its last slot.  A window closed by .x is the previous
+//     lane's scan value plus H, one closed by .y the lane's own scan value: the closing lanes
+//     store, up to 128 windows per row from up to 64 lanes.  What follows the row's last
+//     boundary is the scan value of the lane with the row's last valid slot and becomes lane 0's
+//     partial of the new open window.
+// The unaligned head slot (slot 0) is read up front and starts lane 0's partial, or is window 0
+// by itself; the edge lane of the partial chunk is masked out of its row by the row's valid slot
+// count, as the NaN padding is, and the tail slot joins the window still open at the end.  The
+// sum of a window adds its slots in one order fixed by W, the alignment and the parity of the
+// segment's start: no atomics, the same bits on every launch whatever outputs are null.
+// MM = false: the launch without wmin and wmax (a mean needs neither) leaves the extrema out of the
+// row step; the sum's additions are the same instructions in the same order either way.
+// A lane without a source takes 0.  With every row enabled that is the DPP bound control and the
+// move needs no prepared destination; a masked row keeps the 0 it is given.
+template <int CTRL, int MASK>
+__device__ __forceinline__ uint32_t dpp_take32(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, MASK, 0xF, MASK == 0xF);
+}
+template <int CTRL, int MASK>
+__device__ __forceinline__ uint64_t dpp_take64(uint64_t x) {
+    return ((uint64_t)dpp_take32<CTRL, MASK>((uint32_t)(x >> 32)) << 32) | dpp_take32<CTRL, MASK>((uint32_t)x);
+}
+// v when take, else a NaN: only the high word decides that
+__device__ __forceinline__ double nan_unless(bool take, uint64_t v) {
+    const uint32_t hi = take ? (uint32_t)(v >> 32) : (uint32_t)(kQuietNaN >> 32);
+    return bitsd(((uint64_t)hi << 32) | (uint32_t)v);
+}
+
+template <bool MM>
+struct RollupProc {
+    double mn, mx, sm;  // per lane: partial of the open window (lanes other than 0 hold the
+    uint32_t nn;        // identity unless spread); nn = its NaN slots
+    uint32_t W, ph;
+    uint32_t reach;     // W / 2: the lanes a window's slots are apart at most
+    uint32_t r0;        // position inside the open window of the row to come
+    int64_t w0;         // index of the open window
+    int64_t left;       // body slots still to come
+    int64_t L;
+    uint32_t full;      // full chunks still to come before the partial one
+    uint32_t nans;      // wave-uniform: NaN slots of the segment
+    bool spread;        // lanes other than 0 may hold partials
+    bool has_tail, gaps;
+    int lane;
+    double* o_mn;       // per-window outputs at the segment's first window; null: not written
+    double* o_mx;
+    double* o_sm;
+    uint32_t* o_cnt;
+
+    template <int CTRL, int MASK>
+    __device__ __forceinline__ static void seg_step(uint32_t key, double& a, double& b, double& c, uint32_t& n) {
+        // keys are window + 1: the 0 a lane without a source takes is no key, and the zeros it takes
+        // for the values are never used
+        const bool same = dpp_take32<CTRL, MASK>(key) == key;
+        if constexpr (MM) {
+            a = fmin(nan_unless(same, dpp_take64<CTRL, MASK>(dbits(a))), a);
+            b = fmax(nan_unless(same, dpp_take64<CTRL, MASK>(dbits(b))), b);
+        }
+        const double pc = bitsd(dpp_take64<CTRL, MASK>(dbits(c)));
+        const uint32_t pn = dpp_take32<CTRL, MASK>(n);
+        c = (same ? pc : 0.0) + c;
+        n += same ? pn : 0u;
+    }
+    // the value of the lane before this one (lane 0: 0)
+    __device__ __forceinline__ uint32_t prev_take32(uint32_t x) const {
+        const uint32_t a = dpp_take32<kDppRowShr1, 0xF>(x);
+        const uint32_t b = dpp_take32<kDppRowBcast15, 0xE>(x);
+        return (lane & 15) ? a : b;
+    }
+    __device__ __forceinline__ uint64_t prev_take64(uint64_t x) const {
+        return ((uint64_t)prev_take32((uint32_t)(x >> 32)) << 32) | prev_take32((uint32_t)x);
+    }
+
+    // the slots of window w, whichever it is
+    __device__ __forceinline__ uint32_t slots_of(int64_t w) const {
+        const int64_t lo = w * (int64_t)W - (int64_t)ph, hi = lo + (int64_t)W;
+        return (uint32_t)((hi < L ? hi : L) - (lo > 0 ? lo : 0));
+    }
+
+    __device__ __forceinline__ void emit(bool on, int64_t w, uint32_t slots, double emn, double emx, double esm,
+                                         uint32_t enn) const {
+        if (!on) return;
+        const bool bad = !gaps && enn;
+        const uint32_t n = gaps ? slots - enn : slots;
+        if constexpr (MM) {
+            uint64_t bmn = dbits(emn), bmx = dbits(emx);
+            if (is_zero_bits(bmn)) bmn = 0;
+            if (is_zero_bits(bmx)) bmx = 0;
+            if (bad || n == 0) bmn = bmx = kQuietNaN;
+            if (o_mn) o_mn[w] = bitsd(bmn);
+            if (o_mx) o_mx[w] = bitsd(bmx);
+        }
+        if (o_sm) o_sm[w] = bad ? bitsd(kQuietNaN) : esm;
+        if (o_cnt) o_cnt[w] = n;
+    }
+
+    // all lanes' partials into lane 0
+    __device__ __forceinline__ void gather() {
+        const bool l0 = lane == 0;
+        if constexpr (MM) {
+            const double fa = wave_min_f64(mn), fb = wave_max_f64(mx);
+            mn = l0 ? fa : bitsd(kQuietNaN);
+            mx = l0 ? fb : bitsd(kQuietNaN);
+        }
+        const double fc = wave_sum_f64(sm);
+        const uint32_t fn = wave_sum_u32(nn);
+        sm = l0 ? fc : 0.0;
+        nn = l0 ? fn : 0u;
+        spread = false;
+    }
+
+    // lim = the row's valid slots, 1..128 (wave-uniform): the slots from lim on are padding or the edge lane
+    __device__ __forceinline__ void row(double x, double y, uint32_t lim) {
+        const uint32_t jx = 2u * (uint32_t)lane, jy = jx + 1u;
+        bool nx = __builtin_isnan(x), ny = __builtin_isnan(y);
+        if (lim < 2u * kWave) {
+            const bool vx = jx < lim, vy = jy < lim;
+            x = vx ? x : bitsd(kQuietNaN);
+            y = vy ? y : bitsd(kQuietNaN);
+            nx = nx && vx;
+            ny = ny && vy;
+        }
+        nans += popc64(ballot(nx)) + popc64(ballot(ny));
+        const double sx = __builtin_isnan(x) ? 0.0 : x, sy = __builtin_isnan(y) ? 0.0 : y;
+        const uint32_t cx = nx ? 1u : 0u, cy = ny ? 1u : 0u;
+        left -= lim;
+        if (r0 + lim < W) {  // no window closes in this row
+            if constexpr (MM) {
+                mn = fmin(fmin(mn, x), y);
+                mx = fmax(fmax(mx, x), y);
+            }
+            sm += sx;
+            sm += sy;
+            nn += cx + cy;
+            r0 += lim;
+            spread = true;
+            return;
+        }
+        if (spread) gather();
+        const uint32_t k = (r0 + lim) / W;  // windows closing in this row: >= 1
+        const uint32_t tx = r0 + jx;
+        uint32_t wx = tx / W;
+        const uint32_t rx = tx - wx * W;
+        uint32_t wy = wx, ry = rx + 1u;
+        if (ry >= W) {
+            ++wy;
+            ry = 0u;
+        }
+        uint32_t wn = ry + 1u >= W ? wy + 1u : wy;  // the window of the next lane's .x
+        if (lim < 2u * kWave) {
+            wx = jx < lim ? wx : k;
+            wy = jy < lim ? wy : k;
+            wn = jy + 1u < lim ? wn : k;
+        }
+        const bool split = wx != wy;  // .x is the last slot of its window
+        const double qn = bitsd(kQuietNaN);
+        // H: the lane's partial (lane 0: the open window so far) and .x
+        double hmn = qn, hmx = qn, amn = qn, amx = qn;
+        if constexpr (MM) {
+            hmn = fmin(mn, x);
+            hmx = fmax(mx, x);
+        }
+        const double hsm = sm + sx;
+        const uint32_t hnn = nn + cx;
+        // A: what the lane holds of the window of .y
+        if constexpr (MM) {
+            amn = fmin(split ? qn : hmn, y);
+            amx = fmax(split ? qn : hmx, y);
+        }
+        double asm_ = (split ? 0.0 : hsm) + sy;
+        uint32_t ann = (split ? 0u : hnn) + cy;
+        // the lanes of one window are at most `reach` apart: the steps that reach further find no equal key
+        const uint32_t key = wy + 1u;
+        if (reach >= 1) seg_step<kDppRowShr1, 0xF>(key, amn, amx, asm_, ann);
+        if (reach >= 2) seg_step<kDppRowShr2, 0xF>(key, amn, amx, asm_, ann);
+        if (reach >= 4) seg_step<kDppRowShr4, 0xF>(key, amn, amx, asm_, ann);
+        if (reach >= 8) seg_step<kDppRowShr8, 0xF>(key, amn, amx, asm_, ann);
+        if (reach >= 1) {
+            seg_step<kDppRowBcast15, 0xA>(key, amn, amx, asm_, ann);
+            seg_step<kDppRowBcast31, 0xC>(key, amn, amx, asm_, ann);
+        }
+        // a window that closes inside a row has all its W slots, or is window 0 of the end-aligned grid
+        const bool first = w0 == 0;
+        if (ballot(split)) {
+            // a window closed by .x: the slots before it are the previous lane's scan value
+            const bool join = prev_take32(key) == wx + 1u;
+            double emn = qn, emx = qn;
+            if constexpr (MM) {
+                emn = fmin(nan_unless(join, prev_take64(dbits(amn))), hmn);
+                emx = fmax(nan_unless(join, prev_take64(dbits(amx))), hmx);
+            }
+            const double psm = bitsd(prev_take64(dbits(asm_)));
+            const uint32_t pnn = prev_take32(ann);
+            emit(split, w0 + wx, first && wx == 0 ? W - ph : W, emn, emx, (join ? psm : 0.0) + hsm,
+                 (join ? pnn : 0u) + hnn);
+        }
+        emit(wn != wy, w0 + wy, first && wy == 0 ? W - ph : W, amn, amx, asm_, ann);
+        // the slots after the row's last boundary open the next window: the scan value of the lane
+        // that holds the row's last valid slot (the lanes after it in a partial row share its key, but
+        // are further away than the scan has to reach)
+        r0 = r0 + lim - k * W;
+        w0 += k;
+        const bool keep = r0 != 0u && lane == 0;
+        const int src = (int)((lim - 1u) >> 1);
+        if constexpr (MM) {
+            const double tmn = bitsd(lane_bcast64(dbits(amn), src)), tmx = bitsd(lane_bcast64(dbits(amx), src));
+            mn = keep ? tmn : qn;
+            mx = keep ? tmx : qn;
+        }
+        const double tsm = bitsd(lane_bcast64(dbits(asm_), src));
+        const uint32_t tnn = lane_bcast32(ann, src);
+        sm = keep ? tsm : 0.0;
+        nn = keep ? tnn : 0u;
+    }
+
+    __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
+        const bool partial = full == 0;  // wave-uniform
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const uint32_t lim = !partial || left >= 2 * kWave ? 2u * kWave : (uint32_t)left;
+            if (lim) row(c[u].x, c[u].y, lim);
+        }
+        if (partial && has_tail) {  // lane 63 of the partial chunk's last row: .y is the tail slot
+            const double t = c[kUnroll - 1].y;
+            const bool tn = __builtin_isnan(t);
+            if (lane == kWave - 1) {
+                if constexpr (MM) {
+                    mn = fmin(mn, t);
+                    mx = fmax(mx, t);
+                }
+                sm += tn ? 0.0 : t;
+                nn += tn ? 1u : 0u;
+            }
+            nans += (uint32_t)(ballot(tn) >> (kWave - 1));
+            spread = true;
+        }
+        --full;
+    }
+};
+
+struct RollupArgs {
+    const double* vals;
+    const int64_t* offs;
+    const int64_t* woffs;
+    int64_t S;
+    int64_t W;
+    int32_t align_end;
+    int32_t gaps;
+    int32_t remap;  // xcd_item, chosen as max_args chooses it
+    double* out_wmin;  // the four per-window outputs may each be null
+    double* out_wmax;
+    double* out_wsum;
+    uint32_t* out_wcnt;
+    int64_t* out_n;
+    uint32_t* out_f;
+};
+
+// The row step is large, so the skeleton's single-site loop (one inlined chunk body), as k_exceed.
+template <bool MM>
+__global__ __launch_bounds__(64) void k_rollup(RollupArgs A) {
+    const int lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < A.S; b += gridDim.x) {
+        const int64_t s = xcd_item(b, A.S, A.remap);
+        const int64_t beg = A.offs[s], end = A.offs[s + 1];
+        const int64_t wbeg = A.woffs[s], wend = A.woffs[s + 1];
+        const int64_t L = end > beg ? end - beg : 0;
+        const int64_t nw = (L + A.W - 1) / A.W;
+        const bool fits = wend - wbeg >= nw;
+        int64_t a0 = (beg + 1) & ~(int64_t)1;
+        if (a0 > end) a0 = end;
+        int64_t a1 = end & ~(int64_t)1;
+        if (a1 < a0) a1 = a0;
+        RollupProc<MM> P;
+        P.mn = P.mx = bitsd(kQuietNaN);
+        P.sm = 0.0;
+        P.nn = 0u;
+        P.W = (uint32_t)A.W;
+        P.reach = P.W >> 1;
+        P.ph = A.align_end ? (uint32_t)((A.W - L % A.W) % A.W) : 0u;
+        P.L = L;
+        P.left = a1 - a0;
+        P.full = (uint32_t)(((a1 >> 1) - (a0 >> 1)) / (kUnroll * kWave));
+        P.nans = 0u;
+        P.spread = false;
+        P.has_tail = a1 < end;
+        P.gaps = A.gaps != 0;
+        P.lane = lane;
+        P.o_mn = fits && A.out_wmin ? A.out_wmin + wbeg : nullptr;
+        P.o_mx = fits && A.out_wmax ? A.out_wmax + wbeg : nullptr;
+        P.o_sm = fits && A.out_wsum ? A.out_wsum + wbeg : nullptr;
+        P.o_cnt = fits && A.out_wcnt ? A.out_wcnt + wbeg : nullptr;
+        const bool head = a0 > beg;
+        const uint64_t pos = (uint64_t)P.ph + (head ? 1u : 0u);  // position of the first body slot: <= W
+        P.w0 = pos >= (uint64_t)A.W ? 1 : 0;
+        P.r0 = (uint32_t)(pos >= (uint64_t)A.W ? pos - (uint64_t)A.W : pos);
+        if (head) {  // slot 0, in the first chunk's cache line: it arrives with the LAST chunk
+            const double h = A.vals[beg];
+            const bool hn = __builtin_isnan(h);
+            P.nans += hn ? 1u : 0u;
+            if (P.w0) {  // window 0 by itself
+                P.emit(lane == 0, 0, 1u, h, h, hn ? 0.0 : h, hn ? 1u : 0u);
+            } else if (lane == 0) {
+                P.mn = P.mx = h;
+                P.sm = hn ? 0.0 : h;
+                P.nn = hn ? 1u : 0u;
+            }
+        }
+        stream_segment<true>(A.vals, beg, end, P, lane);
+        if (P.w0 < nw) {  // the window still open at the segment's end
+            P.gather();
+            P.emit(lane == 0, P.w0, P.slots_of(P.w0), P.mn, P.mx, P.sm, P.nn);
+        }
+        const uint64_t n = A.gaps ? (uint64_t)L - P.nans : (uint64_t)L;
+        uint32_t flags = 0;
+        if (n == 0) flags = KRR_FLAG_EMPTY;
+        else if (P.nans && !A.gaps) flags = KRR_FLAG_NAN;
+        if (!fits) flags |= KRR_FLAG_CAPACITY;
+        if (lane == 0) {
+            A.out_n[s] = (int64_t)n;
+            A.out_f[s] = flags;
+        }
+    }
+}
+
 }  // namespace krr
 #include "krr_kll.h"
 namespace krr {
@@ -4463,6 +4798,33 @@ int krr_segmented_exceed(krr_ctx* ctx, const krr_series* series, const double* t
         case 3: hipLaunchKernelGGL(k_exceed<3>, grid, block, 0, st, A); break;
         default: hipLaunchKernelGGL(k_exceed<4>, grid, block, 0, st, A); break;
     }
+    KRR_HIP(ctx, hipGetLastError());
+    return KRR_OK;
+}
+
+int krr_segmented_rollup(krr_ctx* ctx, const krr_series* series, int64_t window, int32_t align,
+                         const int64_t* win_offsets, double* out_wmin, double* out_wmax, double* out_wsum,
+                         uint32_t* out_wcount, int64_t* out_count, uint32_t* out_flags, void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    int rc = check_series(ctx, series);
+    if (rc) return rc;
+    if (window < 1 || window > 2147483647ll)
+        return set_err(ctx, KRR_E_INVALID, "window outside 1..2^31-1%s: %lld", "", (long long)window);
+    if (align != KRR_ROLLUP_START && align != KRR_ROLLUP_END)
+        return set_err(ctx, KRR_E_INVALID, "align is neither KRR_ROLLUP_START nor KRR_ROLLUP_END%s: %lld", "",
+                       (long long)align);
+    const int64_t S = series->n_segments;
+    if (S == 0) return KRR_OK;
+    if (!win_offsets || !out_count || !out_flags)
+        return set_err(ctx, KRR_E_INVALID, "null win_offsets or outputs%s", "");
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    const MaxArgs M = max_args(series, nullptr, out_count, out_flags, nullptr);  // its remap choice
+    const RollupArgs A{series->values, series->offsets, win_offsets, S,        window,     align == KRR_ROLLUP_END,
+                       series->gaps_are_nan, M.remap,   out_wmin,    out_wmax, out_wsum,   out_wcount,
+                       out_count,      out_flags};
+    if (out_wmin || out_wmax) hipLaunchKernelGGL(k_rollup<true>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(k_rollup<false>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
     KRR_HIP(ctx, hipGetLastError());
     return KRR_OK;
 }
