@@ -472,6 +472,14 @@ def allocation_thresholds(objects: Sequence, resource: ResourceType, which: str 
     return out
 
 
+def _slots(ps: PackedSeries) -> np.ndarray:
+    """int64 [S]: each series' length in slots, from the offsets wherever they live."""
+    offs = ps.offsets
+    if not isinstance(offs, np.ndarray) and hasattr(offs, "is_cuda"):
+        offs = offs.cpu().numpy()
+    return np.diff(np.asarray(offs, dtype=np.int64))
+
+
 class FleetBatch:
     """A fleet's histories as device-side series, with cached per-object statistics.
 
@@ -545,12 +553,8 @@ class FleetBatch:
         if mo is None:
             ps = self.series(resource)
             r = self.engine.moments_series(ps, trend=bool(trend))
-            offs = ps.offsets
-            if not isinstance(offs, np.ndarray) and hasattr(offs, "is_cuda"):
-                offs = offs.cpu().numpy()
-            slots = np.diff(np.asarray(offs, dtype=np.int64))
             mo = self._cache[(resource, "moments", bool(trend))] = FleetMoments(
-                r["count"], r["mean"], r["m2"], r.get("tmean"), r.get("t2"), r.get("cxt"), r["flags"], slots)
+                r["count"], r["mean"], r["m2"], r.get("tmean"), r.get("t2"), r.get("cxt"), r["flags"], _slots(ps))
         return mo
 
     def _threshold_rows(self, thresholds, S: int) -> np.ndarray:
@@ -591,12 +595,8 @@ class FleetBatch:
         ex = self._cache.get(key)
         if ex is None:
             r = self.engine.exceed_series(ps, thr)
-            offs = ps.offsets
-            if not isinstance(offs, np.ndarray) and hasattr(offs, "is_cuda"):
-                offs = offs.cpu().numpy()
-            slots = np.diff(np.asarray(offs, dtype=np.int64))
             ex = self._cache[key] = FleetExceedance(r["above"], r["excess"], r["longest"], r["head"], r["tail"],
-                                                    r["last"], thr, r["count"], r["flags"], slots)
+                                                    r["last"], thr, r["count"], r["flags"], _slots(ps))
         return ex
 
     def rollup(self, resource: ResourceType, window: int, align: str = "end") -> FleetRollup:
@@ -623,11 +623,7 @@ class FleetBatch:
             if (r["flags"] & _native.KRR_FLAG_CAPACITY).any():
                 s = int(np.flatnonzero(r["flags"] & _native.KRR_FLAG_CAPACITY)[0])
                 raise RuntimeError(f"object {s}: window offsets too small for its windows (KRR_FLAG_CAPACITY)")
-            offs = ps.offsets
-            if not isinstance(offs, np.ndarray) and hasattr(offs, "is_cuda"):
-                offs = offs.cpu().numpy()
-            slots = np.diff(np.asarray(offs, dtype=np.int64))
-            ru = self._cache[key] = FleetRollup(resource, int(window), align, r["offsets"], slots, r["count"],
+            ru = self._cache[key] = FleetRollup(resource, int(window), align, r["offsets"], _slots(ps), r["count"],
                                                 r["flags"], r["wcount"], r["min"], r["max"], r["sum"],
                                                 self.device, self.engine)
         return ru

@@ -317,10 +317,8 @@ class SimpleEngine:
         the current stream, with one synchronisation at the end."""
         ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
         parts = [self._stats_part(ctx, part) for part in self._series_parts(ps)]
-        host = self._host_concat(parts, {"min": np.float64, "max": np.float64, "sum": np.float64,
+        return self._host_concat(parts, {"min": np.float64, "max": np.float64, "sum": np.float64,
                                          "count": np.int64, "flags": np.int32})
-        host["flags"] = host["flags"].view(np.uint32)
-        return host
 
     def moments_series(self, ps: PackedSeries, trend: bool = True) -> dict:
         """Mean and centred second moments of every segment of one series
@@ -331,9 +329,7 @@ class SimpleEngine:
         ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
         parts = [self._moments_part(ctx, part, trend) for part in self._series_parts(ps)]
         dtypes = {k: np.float64 for k in (("mean", "m2", "tmean", "t2", "cxt") if trend else ("mean", "m2"))}
-        host = self._host_concat(parts, {**dtypes, "count": np.int64, "flags": np.int32})
-        host["flags"] = host["flags"].view(np.uint32)
-        return host
+        return self._host_concat(parts, {**dtypes, "count": np.int64, "flags": np.int32})
 
     def exceed_series(self, ps: PackedSeries, thresholds) -> dict:
         """Per segment and threshold, the samples above it (krr_segmented_exceed): host arrays
@@ -362,11 +358,9 @@ class SimpleEngine:
                 out = {**out, **{k: torch.cat([g[k] for g in groups], dim=0) for k in ints + ("excess",)}}
             parts.append(out)
             lo = hi
-        host = self._host_concat(parts, {**{k: np.int64 for k in ints}, "excess": np.float64,
+        return self._host_concat(parts, {**{k: np.int64 for k in ints}, "excess": np.float64,
                                          "count": np.int64, "flags": np.int32},
                                  rows={**{k: R for k in ints}, "excess": R})
-        host["flags"] = host["flags"].view(np.uint32)
-        return host
 
     def rollup_series(self, ps: PackedSeries, window: int, align: int) -> dict:
         """Every segment of one series cut into windows of ``window`` slots
@@ -398,7 +392,7 @@ class SimpleEngine:
             res = {k: torch.cat([p[k] for p in parts]) for k, _ in names}
         host = self._host_concat([{k: p[k] for k in ("count", "flags")} for p in parts],
                                  {"count": np.int64, "flags": np.int32})
-        res.update(offsets=np.concatenate(woffs), count=host["count"], flags=host["flags"].view(np.uint32))
+        res.update(offsets=np.concatenate(woffs), count=host["count"], flags=host["flags"])
         return res
 
     def _rollup_part(self, ctx, part: PackedSeries, window: int, align: int) -> tuple:
@@ -421,11 +415,9 @@ class SimpleEngine:
                              out=d_wo[1:])
                 wo = d_wo.cpu().numpy()
             nwin = int(wo[-1])
-            out = {"wcount": torch.empty(nwin, dtype=torch.int32, device=dev)}
-            for k in ("min", "max", "sum"):
-                out[k] = torch.empty(nwin, dtype=torch.float64, device=dev)
-            out["count"] = torch.empty(n, dtype=torch.int64, device=dev)
-            out["flags"] = torch.empty(n, dtype=torch.int32, device=dev)
+            out = {**self._outputs((("wcount", torch.int32, 0), ("min", torch.float64, 0), ("max", torch.float64, 0),
+                                     ("sum", torch.float64, 0)), nwin),
+                   **self._outputs((("count", torch.int64, 0), ("flags", torch.int32, 0)), n)}
             ctx.segmented_rollup(series, window, align, d_wo, out["min"], out["max"], out["sum"], out["wcount"],
                                  out["count"], out["flags"])
         return out, wo
@@ -444,7 +436,7 @@ class SimpleEngine:
         parts = [self._percentiles_part(ctx, part, params_list) for part in self._series_parts(ps)]
         host = self._host_concat(parts, {"value": np.float64, "count": np.int64, "flags": np.int32},
                                  rows={"value": len(params_list), "flags": len(params_list)})
-        return host["value"], host["count"], host["flags"].view(np.uint32)
+        return host["value"], host["count"], host["flags"]
 
     def _series_parts(self, ps: PackedSeries):
         """The whole-segment ranges one series runs as — ``_chunk_bounds``' rule for a single
@@ -476,13 +468,10 @@ class SimpleEngine:
         chunk's device tensors."""
         import torch
 
-        dev = torch.device("cuda", self.device)
         with torch.cuda.device(self.device):
             series = self._part_series(ctx, part)
-            n = part.n_segments
-            out = {k: torch.empty(n, dtype=dt, device=dev) for k, dt in
-                   (("min", torch.float64), ("max", torch.float64), ("sum", torch.float64),
-                    ("count", torch.int64), ("flags", torch.int32))}
+            out = self._outputs((("min", torch.float64, 0), ("max", torch.float64, 0), ("sum", torch.float64, 0),
+                                 ("count", torch.int64, 0), ("flags", torch.int32, 0)), part.n_segments)
             ctx.segmented_stats(series, out["min"], out["max"], out["sum"], out["count"], out["flags"])
         return out
 
@@ -491,14 +480,11 @@ class SimpleEngine:
         chunk's device tensors (without ``trend``: no tmean / t2 / cxt)."""
         import torch
 
-        dev = torch.device("cuda", self.device)
         with torch.cuda.device(self.device):
             series = self._part_series(ctx, part)
-            n = part.n_segments
             names = ("mean", "m2", "tmean", "t2", "cxt") if trend else ("mean", "m2")
-            out = {k: torch.empty(n, dtype=torch.float64, device=dev) for k in names}
-            out["count"] = torch.empty(n, dtype=torch.int64, device=dev)
-            out["flags"] = torch.empty(n, dtype=torch.int32, device=dev)
+            out = self._outputs([*((k, torch.float64, 0) for k in names), ("count", torch.int64, 0),
+                                 ("flags", torch.int32, 0)], part.n_segments)
             ctx.segmented_moments(series, out["mean"], out["m2"], out.get("tmean"), out.get("t2"), out.get("cxt"),
                                   out["count"], out["flags"])
         return out
@@ -514,11 +500,8 @@ class SimpleEngine:
         with torch.cuda.device(self.device):
             series = self._part_series(ctx, part)
             thr = torch.from_numpy(np.ascontiguousarray(thresholds, dtype=np.float64)).to(dev)
-            out = {k: torch.empty((R, n), dtype=torch.int64, device=dev)
-                   for k in ("above", "longest", "head", "tail", "last")}
-            out["excess"] = torch.empty((R, n), dtype=torch.float64, device=dev)
-            out["count"] = torch.empty(n, dtype=torch.int64, device=dev)
-            out["flags"] = torch.empty(n, dtype=torch.int32, device=dev)
+            out = self._outputs((*((k, torch.int64, R) for k in ("above", "longest", "head", "tail", "last")),
+                                 ("excess", torch.float64, R), ("count", torch.int64, 0), ("flags", torch.int32, 0)), n)
             ctx.segmented_exceed(series, thr, R, out["above"], out["excess"], out["longest"], out["head"],
                                  out["tail"], out["last"], out["count"], out["flags"])
         return out
@@ -546,16 +529,29 @@ class SimpleEngine:
         return {"value": value, "count": count, "flags": flags}
 
     def _host_concat(self, parts: list, dtypes: dict, rows: Optional[dict] = None) -> dict:
-        """The chunks' tensors as host arrays, concatenated in segment order (the last axis);
-        synchronises the current stream once, before the first copy."""
+        """The chunks' tensors as host arrays, concatenated in segment order (the last axis), the
+        int32 ``flags`` the kernels wrote viewed as the uint32 they are; synchronises the current
+        stream once, before the first copy."""
         import torch
 
         rows = rows or {}
         if not parts:  # a series without segments launches nothing
-            return {k: np.zeros((rows[k], 0) if k in rows else 0, dtype=dt) for k, dt in dtypes.items()}
-        if any(t.is_cuda for p in parts for t in p.values()):
-            torch.cuda.current_stream(self.device).synchronize()
-        return {k: np.concatenate([p[k].cpu().numpy() for p in parts], axis=-1) for k in dtypes}
+            host = {k: np.zeros((rows[k], 0) if k in rows else 0, dtype=dt) for k, dt in dtypes.items()}
+        else:
+            if any(t.is_cuda for p in parts for t in p.values()):
+                torch.cuda.current_stream(self.device).synchronize()
+            host = {k: np.concatenate([p[k].cpu().numpy() for p in parts], axis=-1) for k in dtypes}
+        if "flags" in host:
+            host["flags"] = host["flags"].view(np.uint32)
+        return host
+
+    def _outputs(self, spec, n: int) -> dict:
+        """Uninitialised device tensors for one launch: per ``(name, dtype, rows)`` of ``spec`` a
+        [rows, n] tensor, [n] where rows is 0."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        return {k: torch.empty((rows, n) if rows else (n,), dtype=dt, device=dev) for k, dt, rows in spec}
 
     def run_packed_multi(self, fleet: PackedFleet, params_list, aggregation: str = "concat",
                          return_pods: bool = False) -> list:
@@ -631,8 +627,6 @@ class SimpleEngine:
                     ("mem_flags", torch.int32, 0))
         pod_keys = (("pod_value", torch.float64, P), ("pod_count", torch.int64, 0), ("pod_flags", torch.int32, P))
 
-        def block(keys, n):
-            return {k: torch.empty((rows, n) if rows else (n,), dtype=dt, device=dev) for k, dt, rows in keys}
 
         locate = any(needs_locate(fleet, params) for params in params_list)
         loc = {r: tuple(np.full(S, -1, dtype=np.int64) for _ in range(3)) for r in ("cpu", "mem")} if locate else None
@@ -642,7 +636,7 @@ class SimpleEngine:
                 if params.mode == _native.KRR_PCT_SORTED_LOWER:
                     pod_locs[j] = {"cpu": tuple(np.full(n_pods, -1, dtype=np.int64) for _ in range(3))}
         with torch.cuda.device(self.device):
-            out = block(obj_keys, S)
+            out = self._outputs(obj_keys, S)
             pod_chunks = {k: [] for k, _, _ in pod_keys}
             pod_lo = 0
             for lo, hi, part, cs, ms in self._chunks(fleet):
@@ -650,7 +644,7 @@ class SimpleEngine:
                 n = view.n_segments
                 whole = hi - lo == S
                 # a chunk's rows are not contiguous in the [P, S] outputs: its own [P, n] block
-                chunk = dict(out if whole else block(obj_keys, hi - lo), **block(pod_keys, n))
+                chunk = dict(out if whole else self._outputs(obj_keys, hi - lo), **self._outputs(pod_keys, n))
                 ctx.simple_run_pods_multi(pcs, pg, ms, params_list, chunk)
                 if not whole:
                     for k, v in out.items():

@@ -7,9 +7,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "krr_plan.h"  // kWave
+
 namespace krr {
 
-constexpr int kWave = 64;
 constexpr uint64_t kSignBit = 0x8000000000000000ull;
 constexpr uint64_t kQuietNaN = 0x7FF8000000000000ull;
 

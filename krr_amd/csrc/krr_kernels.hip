@@ -31,6 +31,7 @@
 #include "krr_amd.h"
 #include "krr_device.h"
 #include "krr_plan.h"
+#include "krr_geom.h"
 #include "krr_json.h"
 
 #ifndef KRR_STREAM_DEPTH
@@ -143,15 +144,14 @@ __device__ __forceinline__ int64_t xcd_item(int64_t i, int64_t n, int32_t remap)
 }
 
 // ---------------------------------------------------------------------------
-// Streaming skeleton.  One wave walks values[beg, end): the 16-byte aligned
-// body in chunks of kUnroll x 16 B per lane (8 KiB per wave), the next chunk
-// in flight while this one is processed.  The partial last chunk is padded
-// with NaN and carries the unaligned head/tail elements in its last slot
-// (lane 63, which a partial chunk never fills), so every chunk goes through
-// the same `proc.chunk(c)` body: a NaN is never a candidate, never a tie and is
-// ignored by fmax, and the padding count is returned so NaN counts can be
-// corrected.  ONE_SITE keeps a single inlined chunk body (register rotation,
-// one 64-bit move per slot) for processors whose body is large.
+// Streaming skeleton.  One wave walks values[beg, end) in the layout of
+// krr_geom.h (chunks of kUnroll x 16 B per lane, 8 KiB per wave), the next chunk
+// in flight while this one is processed.  Every chunk, the padded partial one
+// included, goes through the same `proc.chunk(c)` body: a NaN is never a
+// candidate, never a tie and is ignored by fmax, and the padding count is
+// returned so NaN counts can be corrected.  ONE_SITE keeps a single inlined
+// chunk body (register rotation, one 64-bit move per slot) for processors
+// whose body is large.
 // ---------------------------------------------------------------------------
 #ifndef KRR_NT_LOADS
 #define KRR_NT_LOADS 1  // nontemporal (streaming) policy on the once-read value stream (0: default policy)
@@ -179,19 +179,11 @@ __device__ __forceinline__ void load_chunk(double2 (&c)[kUnroll], const double2*
 template <bool ONE_SITE, class Proc, int DEPTH = KRR_ONE_SITE_DEPTH>
 __device__ __forceinline__ uint32_t stream_segment(const double* __restrict__ vals, int64_t beg,
                                                    int64_t end, Proc& proc, int lane) {
-    int64_t a0 = (beg + 1) & ~(int64_t)1;
-    if (a0 > end) a0 = end;
-    int64_t a1 = end & ~(int64_t)1;
-    if (a1 < a0) a1 = a0;
+    const SegGeom g = seg_geom(beg, end);
     const double2* __restrict__ v2 = reinterpret_cast<const double2*>(vals);
-    const int64_t i0 = a0 >> 1;
-    const int64_t nunits = (a1 >> 1) - i0;
-    constexpr int CH = kUnroll * kWave;  // double2 units per chunk
-    const int64_t nfull = nunits / CH;
-    const int64_t rem = nunits - nfull * CH;
-    const bool head = a0 > beg, tail = a1 < end;
-    const bool partial = rem > 0 || head || tail;
-    const int64_t nch = nfull + (partial ? 1 : 0);
+    constexpr int CH = kChunkUnits;
+    const int64_t a1 = g.a1, i0 = g.i0, nunits = g.nunits, nfull = g.nfull, nch = g.nch();
+    const bool head = g.head, tail = g.tail;
     if (nch == 0) return 0;
     const double2* __restrict__ p = v2 + i0 + lane;
     const double qnan = __builtin_nan("");
@@ -328,7 +320,7 @@ __device__ __forceinline__ uint32_t stream_segment(const double* __restrict__ va
             if (ci + 3 < nch) fill(b1, ci + 3);
         }
     }
-    return partial ? (uint32_t)(2 * CH - 2 * rem - (head ? 1 : 0) - (tail ? 1 : 0)) : 0u;
+    return g.padding();
 }
 
 __device__ __forceinline__ double slot_val(const double2 (&c)[kUnroll], int j) {
@@ -3211,42 +3203,66 @@ __device__ __forceinline__ double wave_sum_f64(double x) {  // identity +0.0
     return bitsd(lane_bcast64(wave_scan64(dbits(x), 0ull, OpAddF64Bits{}), kWave - 1));
 }
 
-struct StatsArgs {
+// The frame of the per-series fleet kernels (k_stats, k_moments, k_exceed, k_rollup): the series,
+// the launch's xcd_item choice (xcd_remap) and the count and flags every one of them writes.
+struct SeriesArgs {
     const double* vals;
     const int64_t* offs;
     int64_t S;
     int32_t gaps;
-    int32_t remap;  // xcd_item, chosen as max_args chooses it
+    int32_t remap;
+    int64_t* out_n;
+    uint32_t* out_f;
+};
+struct SeriesItem {
+    int64_t s, beg, end;
+};
+// the segment block b works on
+__device__ __forceinline__ SeriesItem series_item(const SeriesArgs& H, int64_t b) {
+    const int64_t s = xcd_item(b, H.S, H.remap);
+    return SeriesItem{s, H.offs[s], H.offs[s + 1]};
+}
+// Count and flags of a segment of L slots, `present` of them not NaN.  Lane 0 calls write() where it
+// stores the kernel's other outputs: a second store block per segment costs k_stats two VGPRs.
+struct SeriesCount {
+    uint64_t n;
+    uint32_t flags;
+    __device__ __forceinline__ void write(const SeriesArgs& H, int64_t s) const {
+        H.out_n[s] = (int64_t)n;
+        H.out_f[s] = flags;
+    }
+};
+__device__ __forceinline__ SeriesCount series_count(const SeriesArgs& H, uint64_t L, uint64_t present) {
+    SeriesCount c{H.gaps ? present : L, 0u};
+    if (c.n == 0) c.flags = KRR_FLAG_EMPTY;
+    else if (present != L && !H.gaps) c.flags = KRR_FLAG_NAN;
+    return c;
+}
+
+struct StatsArgs {
+    SeriesArgs h;
     double* out_min;  // may be null
     double* out_max;  // may be null
     double* out_sum;  // may be null
-    int64_t* out_n;
-    uint32_t* out_f;
 };
 
 __global__ __launch_bounds__(64) void k_stats(StatsArgs A) {
     const int lane = threadIdx.x;
-    for (int64_t b = blockIdx.x; b < A.S; b += gridDim.x) {
-        const int64_t s = xcd_item(b, A.S, A.remap);
-        const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    for (int64_t b = blockIdx.x; b < A.h.S; b += gridDim.x) {
+        const auto [s, beg, end] = series_item(A.h, b);
         StatsProc P{__builtin_nan(""), __builtin_nan(""), 0.0, 0u};
-        P.nn -= stream_segment<false>(A.vals, beg, end, P, lane);
+        P.nn -= stream_segment<false>(A.h.vals, beg, end, P, lane);
         const uint64_t L = (uint64_t)(end - beg);
-        const uint64_t n = A.gaps ? L - P.nn : L;
+        const SeriesCount cnt = series_count(A.h, L, L - P.nn);
+        const uint32_t flags = cnt.flags;
         const double mx = wave_max_f64(P.mx), mn = wave_min_f64(P.mn), sm = wave_sum_f64(P.sm);
-        double rmax = bitsd(kQuietNaN), rmin = bitsd(kQuietNaN), rsum = 0.0;
-        uint32_t flags = 0;
-        if (n == 0) {
-            flags = KRR_FLAG_EMPTY;
-        } else if (P.nn && !A.gaps) {
-            flags = KRR_FLAG_NAN;
-            rsum = bitsd(kQuietNaN);
-        } else {
+        double rmax = bitsd(kQuietNaN), rmin = bitsd(kQuietNaN), rsum = flags & KRR_FLAG_NAN ? bitsd(kQuietNaN) : 0.0;
+        if (!flags) {
             // Python max() / min() keep the FIRST extremal element; only +-0 compare equal with
             // different bits, and an extremum of zero is the segment's first zero either way.
             uint64_t bmax = uni64(dbits(mx)), bmin = uni64(dbits(mn));
             if (is_zero_bits(bmax) || is_zero_bits(bmin)) {
-                const uint64_t z = nth_zero_bits(A.vals, beg, end, 0, lane);
+                const uint64_t z = nth_zero_bits(A.h.vals, beg, end, 0, lane);
                 if (is_zero_bits(bmax)) bmax = z;
                 if (is_zero_bits(bmin)) bmin = z;
             }
@@ -3258,8 +3274,7 @@ __global__ __launch_bounds__(64) void k_stats(StatsArgs A) {
             if (A.out_min) A.out_min[s] = rmin;
             if (A.out_max) A.out_max[s] = rmax;
             if (A.out_sum) A.out_sum[s] = rsum;
-            A.out_n[s] = (int64_t)n;
-            A.out_f[s] = flags;
+            cnt.write(A.h, s);
         }
     }
 }
@@ -3308,32 +3323,19 @@ __device__ __forceinline__ Mom mom_merge(const Mom& a, const Mom& b) {
     return r;
 }
 
-// proc.chunk(c) carries no position, so the processor rebuilds stream_segment's geometry from
-// beg / end and counts its chunks: in chunk ci lane l holds, in c[u], the slots
-// a0 - beg + 2 (ci CH + u kWave + l) and the next one, and in the partial last chunk lane 63's
-// c[kUnroll - 1] holds the unaligned head (slot 0) in .x and the unaligned tail (slot L - 1)
-// in .y.  Padding is NaN and therefore absent.
+// The slot index t of a sample comes from the position contract of krr_geom.h (SegCursor).
 template <bool TREND>
 struct MomentsProc {
     Mom run;
-    double t0;     // slot index of c[0].x in the chunk to come
+    SegCursor at;
+    double t0;     // at.base + 2 lane, kept as a double: slot index of c[0].x in the chunk to come
     double tlast;  // L - 1
-    int64_t full;  // full chunks still to come before the partial one
-    bool last_lane;
-    __device__ __forceinline__ MomentsProc(int64_t beg, int64_t end, int lane) {
-        int64_t a0 = (beg + 1) & ~(int64_t)1;
-        if (a0 > end) a0 = end;
-        int64_t a1 = end & ~(int64_t)1;
-        if (a1 < a0) a1 = a0;
-        full = ((a1 >> 1) - (a0 >> 1)) / (kUnroll * kWave);
-        t0 = (double)(a0 - beg + 2 * lane);
-        tlast = (double)(end - beg - 1);
-        last_lane = lane == kWave - 1;
-        run = Mom{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    }
+    __device__ __forceinline__ MomentsProc(int64_t beg, int64_t end, int lane)
+        : run{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, at(seg_geom(beg, end), lane), t0((double)(at.base + 2 * lane)),
+          tlast((double)(end - beg - 1)) {}
     __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
         constexpr int N = 2 * kUnroll;
-        const bool edge = full == 0 && last_lane;  // this lane's last unit is (head, tail)
+        const bool edge = at.edge(kUnroll - 1);  // this lane's last unit is (head, tail)
         // slot index of slot j: rebuilt where it is used (an exact sum), not held in 32 VGPRs
         auto t = [&](int j) {
             const double tj = t0 + (double)((j >> 1) * 2 * kWave + (j & 1));
@@ -3368,8 +3370,8 @@ struct MomentsProc {
             }
         }
         run = mom_merge<TREND>(run, b);
-        t0 += (double)(2 * kUnroll * kWave);
-        --full;
+        t0 += (double)(2 * kChunkUnits);
+        at.next();
     }
 };
 
@@ -3403,18 +3405,12 @@ __device__ __forceinline__ Mom wave_moments(Mom x) {
 }
 
 struct MomentsArgs {
-    const double* vals;
-    const int64_t* offs;
-    int64_t S;
-    int32_t gaps;
-    int32_t remap;     // xcd_item, chosen as max_args chooses it
+    SeriesArgs h;
     double* out_mean;  // may be null
     double* out_m2;    // may be null
     double* out_tmean;  // TREND: required
     double* out_t2;
     double* out_cxt;
-    int64_t* out_n;
-    uint32_t* out_f;
 };
 
 // The TREND body is large, so it takes the skeleton's single-site loop (one inlined chunk body,
@@ -3429,19 +3425,19 @@ struct MomentsArgs {
 template <bool TREND>
 __global__ __launch_bounds__(64) void k_moments(MomentsArgs A) {
     const int lane = threadIdx.x;
-    for (int64_t b = blockIdx.x; b < A.S; b += gridDim.x) {
-        const int64_t s = xcd_item(b, A.S, A.remap);
-        const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    for (int64_t b = blockIdx.x; b < A.h.S; b += gridDim.x) {
+        const auto [s, beg, end] = series_item(A.h, b);
         MomentsProc<TREND> P(beg, end, lane);
-        stream_segment<(KRR_MOMENTS_ONE_SITE && TREND)>(A.vals, beg, end, P, lane);
+        stream_segment<(KRR_MOMENTS_ONE_SITE && TREND)>(A.h.vals, beg, end, P, lane);
         const Mom m = wave_moments<TREND>(P.run);
+        // series_count's rule, written out: through the helper k_moments<false> takes 224 VGPRs for 223
         const uint64_t L = (uint64_t)(end - beg);
         const uint64_t present = (uint64_t)m.n;  // the non-NaN slots: padding is NaN too
-        const uint64_t n = A.gaps ? present : L;
-        const double qnan = bitsd(kQuietNaN);
+        const uint64_t n = A.h.gaps ? present : L;
         uint32_t flags = 0;
         if (n == 0) flags = KRR_FLAG_EMPTY;
-        else if (present != L && !A.gaps) flags = KRR_FLAG_NAN;
+        else if (present != L && !A.h.gaps) flags = KRR_FLAG_NAN;
+        const double qnan = bitsd(kQuietNaN);
         if (lane == 0) {
             if (A.out_mean) A.out_mean[s] = flags ? qnan : m.mx;
             if (A.out_m2) A.out_m2[s] = flags ? qnan : m.m2;
@@ -3450,8 +3446,8 @@ __global__ __launch_bounds__(64) void k_moments(MomentsArgs A) {
                 A.out_t2[s] = flags ? qnan : m.t2;
                 A.out_cxt[s] = flags ? qnan : m.c;
             }
-            A.out_n[s] = (int64_t)n;
-            A.out_f[s] = flags;
+            A.h.out_n[s] = (int64_t)n;
+            A.h.out_f[s] = flags;
         }
     }
 }
@@ -3464,10 +3460,8 @@ __global__ __launch_bounds__(64) void k_moments(MomentsArgs A) {
 //
 // Run statistics of a slot sequence are the tuple (n present, a above, h, t, b); two adjacent
 // sequences merge associatively (run_merge), the empty tuple is the identity.  The skeleton
-// hands a chunk over as kUnroll unit rows: in row u lanes 0..63 hold 128 consecutive slots, lane
-// l's .x is slot 2l and .y slot 2l + 1 of the row, rows and chunks in slot order; in the partial
-// last chunk lane 63 of the last row holds the segment's unaligned head (slot 0) in .x and its
-// unaligned tail (slot L - 1) in .y instead of body slots.  A row's tuple comes from four
+// hands a chunk over as kUnroll rows of 128 consecutive slots, the head and tail slot in the
+// partial chunk's edge unit (krr_geom.h).  A row's tuple comes from four
 // ballots (present / above of .x and of .y).  Nothing above: only n moves, and t drops to 0 when
 // a present slot was seen.  No breaker (a present slot that is not above): the row is one run.
 // Otherwise n and a are popcounts, h and t are popcounts of the above masks before the first and
@@ -3504,24 +3498,15 @@ struct ExceedProc {
     RunTuple body[R];    // wave-uniform: the body rows so far
     uint32_t last[R];    // wave-uniform: last body slot above (meaningful once body[r].a > 0)
     uint32_t present;    // wave-uniform: non-NaN slots so far, head and tail slot included
-    uint32_t base;       // slot index of lane 0's .x in the row to come
-    uint32_t full;       // full chunks still to come before the partial one
+    SegCursor at;        // krr_geom.h: where the chunk to come sits
     uint32_t head_p, tail_p;  // the unaligned head / tail slot is present
     uint32_t head_a, tail_a;  // ... and above threshold r: bit r
     uint64_t below, upto;     // per lane: the lanes before this one, and with it
-    bool last_lane;
-    __device__ __forceinline__ ExceedProc(int64_t beg, int64_t end, int lane) {
+    __device__ __forceinline__ ExceedProc(int64_t beg, int64_t end, int lane) : at(seg_geom(beg, end), lane) {
         below = (1ull << lane) - 1;
         upto = below | 1ull << lane;
-        int64_t a0 = (beg + 1) & ~(int64_t)1;
-        if (a0 > end) a0 = end;
-        int64_t a1 = end & ~(int64_t)1;
-        if (a1 < a0) a1 = a0;
-        full = (uint32_t)(((a1 >> 1) - (a0 >> 1)) / (kUnroll * kWave));
-        base = (uint32_t)(a0 - beg);
         present = 0;
         head_p = tail_p = head_a = tail_a = 0u;
-        last_lane = lane == kWave - 1;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             ex[r] = 0.0;
@@ -3530,14 +3515,13 @@ struct ExceedProc {
         }
     }
     __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
-        const bool partial = full == 0;  // wave-uniform
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
             const double x = c[u].x, y = c[u].y;
             uint64_t px = ballot(!__builtin_isnan(x)), py = ballot(!__builtin_isnan(y));
             present += popc64(px) + popc64(py);
-            // lane 63 of a partial chunk's last row: the head and tail slot, not body slots
-            const bool edge = u == kUnroll - 1 && partial;
+            // the row whose last lane holds the head and tail slot, not body slots
+            const bool edge = at.edge_row(u);
             const uint64_t keep = edge ? ~0ull >> 1 : ~0ull;
             if (edge) {
                 head_p = (uint32_t)(px >> 63);
@@ -3546,7 +3530,7 @@ struct ExceedProc {
             px &= keep;
             py &= keep;
             const uint32_t nr = popc64(px) + popc64(py);
-            const bool live = !(edge && last_lane);
+            const bool live = !at.edge(u);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const bool gx = x > tau[r], gy = y > tau[r];
@@ -3611,20 +3595,15 @@ struct ExceedProc {
                 B = run_merge(B, row);
                 const int hx = ax ? 2 * (63 - __clzll((long long)ax)) : -1;
                 const int hy = ay ? 2 * (63 - __clzll((long long)ay)) + 1 : -1;
-                last[r] = base + (uint32_t)(hx > hy ? hx : hy);
+                last[r] = (uint32_t)at.row_base(u) + (uint32_t)(hx > hy ? hx : hy);
             }
-            base += 2 * kWave;
         }
-        --full;
+        at.next();
     }
 };
 
 struct ExceedArgs {
-    const double* vals;
-    const int64_t* offs;
-    int64_t S;
-    int32_t gaps;
-    int32_t remap;      // xcd_item, chosen as max_args chooses it
+    SeriesArgs h;
     const double* thr;  // [R * S], row-major
     int64_t* out_above;    // the six [R * S] outputs may each be null
     double* out_excess;
@@ -3632,8 +3611,6 @@ struct ExceedArgs {
     int64_t* out_head;
     int64_t* out_tail;
     int64_t* out_last;
-    int64_t* out_n;
-    uint32_t* out_f;
 };
 
 // The body holds kUnroll x R row steps, so it takes the skeleton's single-site loop (one inlined
@@ -3641,18 +3618,15 @@ struct ExceedArgs {
 template <int R>
 __global__ __launch_bounds__(64) void k_exceed(ExceedArgs A) {
     const int lane = threadIdx.x;
-    for (int64_t b = blockIdx.x; b < A.S; b += gridDim.x) {
-        const int64_t s = xcd_item(b, A.S, A.remap);
-        const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    for (int64_t b = blockIdx.x; b < A.h.S; b += gridDim.x) {
+        const auto [s, beg, end] = series_item(A.h, b);
         ExceedProc<R> P(beg, end, lane);
 #pragma unroll
-        for (int r = 0; r < R; ++r) P.tau[r] = A.thr[(int64_t)r * A.S + s];
-        stream_segment<true>(A.vals, beg, end, P, lane);
+        for (int r = 0; r < R; ++r) P.tau[r] = A.thr[(int64_t)r * A.h.S + s];
+        stream_segment<true>(A.h.vals, beg, end, P, lane);
         const uint64_t L = (uint64_t)(end - beg);
-        const uint64_t n = A.gaps ? P.present : L;  // padding is NaN: present counts real slots only
-        uint32_t flags = 0;
-        if (n == 0) flags = KRR_FLAG_EMPTY;
-        else if (P.present != L && !A.gaps) flags = KRR_FLAG_NAN;
+        const SeriesCount cnt = series_count(A.h, L, P.present);  // padding is NaN: real slots only
+        const uint32_t flags = cnt.flags;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const double ex = wave_sum_f64(P.ex[r]);
@@ -3661,7 +3635,7 @@ __global__ __launch_bounds__(64) void k_exceed(ExceedArgs A) {
             const RunTuple t = run_merge(run_merge(head, P.body[r]), tail);
             const int64_t last = ta ? (int64_t)L - 1 : P.body[r].a ? (int64_t)P.last[r] : ha ? 0 : -1;
             if (lane == 0) {
-                const int64_t o = (int64_t)r * A.S + s;
+                const int64_t o = (int64_t)r * A.h.S + s;
                 if (A.out_above) A.out_above[o] = flags ? 0 : (int64_t)t.a;
                 if (A.out_excess) A.out_excess[o] = flags & KRR_FLAG_NAN ? bitsd(kQuietNaN) : flags ? 0.0 : ex;
                 if (A.out_longest) A.out_longest[o] = flags ? 0 : (int64_t)t.b;
@@ -3670,10 +3644,7 @@ __global__ __launch_bounds__(64) void k_exceed(ExceedArgs A) {
                 if (A.out_last) A.out_last[o] = flags ? -1 : last;
             }
         }
-        if (lane == 0) {
-            A.out_n[s] = (int64_t)n;
-            A.out_f[s] = flags;
-        }
+        if (lane == 0) cnt.write(A.h, s);
     }
 }
 
@@ -3727,15 +3698,16 @@ struct RollupProc {
     int64_t w0;         // index of the open window
     int64_t left;       // body slots still to come
     int64_t L;
-    uint32_t full;      // full chunks still to come before the partial one
+    SegCursor at;       // krr_geom.h: which chunk is the partial one, which lane its edge
     uint32_t nans;      // wave-uniform: NaN slots of the segment
     bool spread;        // lanes other than 0 may hold partials
     bool has_tail, gaps;
-    int lane;
     double* o_mn;       // per-window outputs at the segment's first window; null: not written
     double* o_mx;
     double* o_sm;
     uint32_t* o_cnt;
+    __device__ __forceinline__ RollupProc(const SegGeom& g, int lane)
+        : left(2 * g.nunits), at(g, lane), has_tail(g.tail) {}
 
     template <int CTRL, int MASK>
     __device__ __forceinline__ static void seg_step(uint32_t key, double& a, double& b, double& c, uint32_t& n) {
@@ -3755,7 +3727,7 @@ struct RollupProc {
     __device__ __forceinline__ uint32_t prev_take32(uint32_t x) const {
         const uint32_t a = dpp_take32<kDppRowShr1, 0xF>(x);
         const uint32_t b = dpp_take32<kDppRowBcast15, 0xE>(x);
-        return (lane & 15) ? a : b;
+        return (at.lane & 15) ? a : b;
     }
     __device__ __forceinline__ uint64_t prev_take64(uint64_t x) const {
         return ((uint64_t)prev_take32((uint32_t)(x >> 32)) << 32) | prev_take32((uint32_t)x);
@@ -3786,7 +3758,7 @@ struct RollupProc {
 
     // all lanes' partials into lane 0
     __device__ __forceinline__ void gather() {
-        const bool l0 = lane == 0;
+        const bool l0 = at.lane == 0;
         if constexpr (MM) {
             const double fa = wave_min_f64(mn), fb = wave_max_f64(mx);
             mn = l0 ? fa : bitsd(kQuietNaN);
@@ -3801,7 +3773,7 @@ struct RollupProc {
 
     // lim = the row's valid slots, 1..128 (wave-uniform): the slots from lim on are padding or the edge lane
     __device__ __forceinline__ void row(double x, double y, uint32_t lim) {
-        const uint32_t jx = 2u * (uint32_t)lane, jy = jx + 1u;
+        const uint32_t jx = 2u * (uint32_t)at.lane, jy = jx + 1u;
         bool nx = __builtin_isnan(x), ny = __builtin_isnan(y);
         if (lim < 2u * kWave) {
             const bool vx = jx < lim, vy = jy < lim;
@@ -3890,7 +3862,7 @@ struct RollupProc {
         // are further away than the scan has to reach)
         r0 = r0 + lim - k * W;
         w0 += k;
-        const bool keep = r0 != 0u && lane == 0;
+        const bool keep = r0 != 0u && at.lane == 0;
         const int src = (int)((lim - 1u) >> 1);
         if constexpr (MM) {
             const double tmn = bitsd(lane_bcast64(dbits(amn), src)), tmx = bitsd(lane_bcast64(dbits(amx), src));
@@ -3904,16 +3876,16 @@ struct RollupProc {
     }
 
     __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
-        const bool partial = full == 0;  // wave-uniform
+        const bool partial = at.partial();
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
             const uint32_t lim = !partial || left >= 2 * kWave ? 2u * kWave : (uint32_t)left;
             if (lim) row(c[u].x, c[u].y, lim);
         }
-        if (partial && has_tail) {  // lane 63 of the partial chunk's last row: .y is the tail slot
+        if (partial && has_tail) {  // the edge unit's .y is the tail slot
             const double t = c[kUnroll - 1].y;
             const bool tn = __builtin_isnan(t);
-            if (lane == kWave - 1) {
+            if (at.edge(kUnroll - 1)) {
                 if constexpr (MM) {
                     mn = fmin(mn, t);
                     mx = fmax(mx, t);
@@ -3924,43 +3896,33 @@ struct RollupProc {
             nans += (uint32_t)(ballot(tn) >> (kWave - 1));
             spread = true;
         }
-        --full;
+        at.next();
     }
 };
 
 struct RollupArgs {
-    const double* vals;
-    const int64_t* offs;
+    SeriesArgs h;
     const int64_t* woffs;
-    int64_t S;
     int64_t W;
     int32_t align_end;
-    int32_t gaps;
-    int32_t remap;  // xcd_item, chosen as max_args chooses it
     double* out_wmin;  // the four per-window outputs may each be null
     double* out_wmax;
     double* out_wsum;
     uint32_t* out_wcnt;
-    int64_t* out_n;
-    uint32_t* out_f;
 };
 
 // The row step is large, so the skeleton's single-site loop (one inlined chunk body), as k_exceed.
 template <bool MM>
 __global__ __launch_bounds__(64) void k_rollup(RollupArgs A) {
     const int lane = threadIdx.x;
-    for (int64_t b = blockIdx.x; b < A.S; b += gridDim.x) {
-        const int64_t s = xcd_item(b, A.S, A.remap);
-        const int64_t beg = A.offs[s], end = A.offs[s + 1];
+    for (int64_t b = blockIdx.x; b < A.h.S; b += gridDim.x) {
+        const auto [s, beg, end] = series_item(A.h, b);
         const int64_t wbeg = A.woffs[s], wend = A.woffs[s + 1];
         const int64_t L = end > beg ? end - beg : 0;
         const int64_t nw = (L + A.W - 1) / A.W;
         const bool fits = wend - wbeg >= nw;
-        int64_t a0 = (beg + 1) & ~(int64_t)1;
-        if (a0 > end) a0 = end;
-        int64_t a1 = end & ~(int64_t)1;
-        if (a1 < a0) a1 = a0;
-        RollupProc<MM> P;
+        const SegGeom g = seg_geom(beg, end);
+        RollupProc<MM> P(g, lane);
         P.mn = P.mx = bitsd(kQuietNaN);
         P.sm = 0.0;
         P.nn = 0u;
@@ -3968,23 +3930,19 @@ __global__ __launch_bounds__(64) void k_rollup(RollupArgs A) {
         P.reach = P.W >> 1;
         P.ph = A.align_end ? (uint32_t)((A.W - L % A.W) % A.W) : 0u;
         P.L = L;
-        P.left = a1 - a0;
-        P.full = (uint32_t)(((a1 >> 1) - (a0 >> 1)) / (kUnroll * kWave));
         P.nans = 0u;
         P.spread = false;
-        P.has_tail = a1 < end;
-        P.gaps = A.gaps != 0;
-        P.lane = lane;
+        P.gaps = A.h.gaps != 0;
         P.o_mn = fits && A.out_wmin ? A.out_wmin + wbeg : nullptr;
         P.o_mx = fits && A.out_wmax ? A.out_wmax + wbeg : nullptr;
         P.o_sm = fits && A.out_wsum ? A.out_wsum + wbeg : nullptr;
         P.o_cnt = fits && A.out_wcnt ? A.out_wcnt + wbeg : nullptr;
-        const bool head = a0 > beg;
+        const bool head = g.head;
         const uint64_t pos = (uint64_t)P.ph + (head ? 1u : 0u);  // position of the first body slot: <= W
         P.w0 = pos >= (uint64_t)A.W ? 1 : 0;
         P.r0 = (uint32_t)(pos >= (uint64_t)A.W ? pos - (uint64_t)A.W : pos);
         if (head) {  // slot 0, in the first chunk's cache line: it arrives with the LAST chunk
-            const double h = A.vals[beg];
+            const double h = A.h.vals[beg];
             const bool hn = __builtin_isnan(h);
             P.nans += hn ? 1u : 0u;
             if (P.w0) {  // window 0 by itself
@@ -3995,20 +3953,14 @@ __global__ __launch_bounds__(64) void k_rollup(RollupArgs A) {
                 P.nn = hn ? 1u : 0u;
             }
         }
-        stream_segment<true>(A.vals, beg, end, P, lane);
+        stream_segment<true>(A.h.vals, beg, end, P, lane);
         if (P.w0 < nw) {  // the window still open at the segment's end
             P.gather();
             P.emit(lane == 0, P.w0, P.slots_of(P.w0), P.mn, P.mx, P.sm, P.nn);
         }
-        const uint64_t n = A.gaps ? (uint64_t)L - P.nans : (uint64_t)L;
-        uint32_t flags = 0;
-        if (n == 0) flags = KRR_FLAG_EMPTY;
-        else if (P.nans && !A.gaps) flags = KRR_FLAG_NAN;
-        if (!fits) flags |= KRR_FLAG_CAPACITY;
-        if (lane == 0) {
-            A.out_n[s] = (int64_t)n;
-            A.out_f[s] = flags;
-        }
+        SeriesCount cnt = series_count(A.h, (uint64_t)L, (uint64_t)L - P.nans);
+        if (!fits) cnt.flags |= KRR_FLAG_CAPACITY;
+        if (lane == 0) cnt.write(A.h, s);
     }
 }
 
@@ -4492,10 +4444,15 @@ int clamp_lds(krr_ctx* ctx, size_t* lds) {
     return KRR_OK;
 }
 
+// xcd_item for a launch over s: on, unless its segments are known to be long (KRR_XCD_REMAP_MAXLEN).
+int32_t xcd_remap(const krr_series* s) {
+    return s->max_segment_len > 0 && s->max_segment_len >= KRR_XCD_REMAP_MAXLEN ? 0 : 1;
+}
+
 // The memory half of a launch (k_max, or the fused kernels' second half).
 MaxArgs max_args(const krr_series* mem, double* value, int64_t* count, uint32_t* flags, int64_t* records) {
     MaxArgs M{mem->values, mem->offsets, mem->n_segments, mem->gaps_are_nan, value, count, flags, records};
-    M.remap = mem->max_segment_len > 0 && mem->max_segment_len >= KRR_XCD_REMAP_MAXLEN ? 0 : 1;
+    M.remap = xcd_remap(mem);
     return M;
 }
 
@@ -4504,6 +4461,29 @@ int check_series(krr_ctx* ctx, const krr_series* s) {
     if (s->n_segments < 0) return set_err(ctx, KRR_E_INVALID, "negative n_segments%s", "");
     if (s->n_segments > 0 && (!s->offsets || (!s->values && s->n_values > 0)))
         return set_err(ctx, KRR_E_INVALID, "null values/offsets%s", "");
+    return KRR_OK;
+}
+
+// The front matter of the per-series entry points (krr_segmented_max, _stats, _moments, _exceed, _rollup):
+// ctx and series, `early` (the outcome of the entry's checks that come before the S == 0 return: set_err
+// ignores a null ctx and check_series overwrites its text, so the entry evaluates them up front), that
+// return, the device, and `run(head, grid)`: the entry's other checks in its order, then its launch.
+template <class Run>
+int series_entry(krr_ctx* ctx, const krr_series* series, int64_t* out_count, uint32_t* out_flags, int early,
+                 Run run) {
+    if (!ctx) return KRR_E_INVALID;
+    int rc = check_series(ctx, series);
+    if (!rc) rc = early;
+    if (rc) return rc;
+    const int64_t S = series->n_segments;
+    if (S == 0) return KRR_OK;
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    rc = run(SeriesArgs{series->values, series->offsets, S, series->gaps_are_nan, xcd_remap(series), out_count,
+                        out_flags},
+             dim3(grid_for(S)));
+    if (rc) return rc;
+    KRR_HIP(ctx, hipGetLastError());
     return KRR_OK;
 }
 
@@ -4715,118 +4695,82 @@ int krr_segmented_percentile(krr_ctx* ctx, const krr_series* series, const krr_p
 
 int krr_segmented_max(krr_ctx* ctx, const krr_series* series, double* out_value, int64_t* out_count,
                       uint32_t* out_flags, void* stream) {
-    if (!ctx) return KRR_E_INVALID;
-    int rc = check_series(ctx, series);
-    if (rc) return rc;
-    const int64_t S = series->n_segments;
-    if (S == 0) return KRR_OK;
-    if (!out_value || !out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-    const MaxArgs A = max_args(series, out_value, out_count, out_flags, nullptr);
-    hipLaunchKernelGGL(k_max, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
-    KRR_HIP(ctx, hipGetLastError());
-    return KRR_OK;
+    return series_entry(ctx, series, out_count, out_flags, KRR_OK, [&](const SeriesArgs&, dim3 grid) -> int {
+        if (!out_value || !out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+        const MaxArgs A = max_args(series, out_value, out_count, out_flags, nullptr);
+        hipLaunchKernelGGL(k_max, grid, dim3(64), 0, (hipStream_t)stream, A);
+        return KRR_OK;
+    });
 }
 
 int krr_segmented_stats(krr_ctx* ctx, const krr_series* series, double* out_min, double* out_max, double* out_sum,
                         int64_t* out_count, uint32_t* out_flags, void* stream) {
-    if (!ctx) return KRR_E_INVALID;
-    int rc = check_series(ctx, series);
-    if (rc) return rc;
-    const int64_t S = series->n_segments;
-    if (S == 0) return KRR_OK;
-    if (!out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-    const MaxArgs M = max_args(series, nullptr, out_count, out_flags, nullptr);  // its remap choice
-    const StatsArgs A{series->values, series->offsets, S,       series->gaps_are_nan, M.remap,
-                      out_min,        out_max,         out_sum, out_count,            out_flags};
-    hipLaunchKernelGGL(k_stats, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
-    KRR_HIP(ctx, hipGetLastError());
-    return KRR_OK;
+    return series_entry(ctx, series, out_count, out_flags, KRR_OK, [&](const SeriesArgs& H, dim3 grid) -> int {
+        if (!out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+        const StatsArgs A{H, out_min, out_max, out_sum};
+        hipLaunchKernelGGL(k_stats, grid, dim3(64), 0, (hipStream_t)stream, A);
+        return KRR_OK;
+    });
 }
 
 int krr_segmented_moments(krr_ctx* ctx, const krr_series* series, double* out_mean, double* out_m2,
                           double* out_tmean, double* out_t2, double* out_cxt, int64_t* out_count,
                           uint32_t* out_flags, void* stream) {
-    if (!ctx) return KRR_E_INVALID;
-    int rc = check_series(ctx, series);
-    if (rc) return rc;
-    const int64_t S = series->n_segments;
-    if (S == 0) return KRR_OK;
-    if (!out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
-    const int n_trend = (out_tmean != nullptr) + (out_t2 != nullptr) + (out_cxt != nullptr);
-    if (n_trend != 0 && n_trend != 3)
-        return set_err(ctx, KRR_E_INVALID, "out_tmean, out_t2 and out_cxt go together%s", "");
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-    const MaxArgs M = max_args(series, nullptr, out_count, out_flags, nullptr);  // its remap choice
-    const MomentsArgs A{series->values, series->offsets, S,      series->gaps_are_nan, M.remap,   out_mean,
-                        out_m2,         out_tmean,       out_t2, out_cxt,              out_count, out_flags};
-    if (n_trend) hipLaunchKernelGGL(k_moments<true>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(k_moments<false>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
-    KRR_HIP(ctx, hipGetLastError());
-    return KRR_OK;
+    return series_entry(ctx, series, out_count, out_flags, KRR_OK, [&](const SeriesArgs& H, dim3 grid) -> int {
+        if (!out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+        const int n_trend = (out_tmean != nullptr) + (out_t2 != nullptr) + (out_cxt != nullptr);
+        if (n_trend != 0 && n_trend != 3)
+            return set_err(ctx, KRR_E_INVALID, "out_tmean, out_t2 and out_cxt go together%s", "");
+        const MomentsArgs A{H, out_mean, out_m2, out_tmean, out_t2, out_cxt};
+        if (n_trend) hipLaunchKernelGGL(k_moments<true>, grid, dim3(64), 0, (hipStream_t)stream, A);
+        else hipLaunchKernelGGL(k_moments<false>, grid, dim3(64), 0, (hipStream_t)stream, A);
+        return KRR_OK;
+    });
 }
 
 int krr_segmented_exceed(krr_ctx* ctx, const krr_series* series, const double* thresholds, int32_t n_thresholds,
                          int64_t* out_above, double* out_excess, int64_t* out_longest, int64_t* out_head,
                          int64_t* out_tail, int64_t* out_last, int64_t* out_count, uint32_t* out_flags,
                          void* stream) {
-    if (!ctx) return KRR_E_INVALID;
-    int rc = check_series(ctx, series);
-    if (rc) return rc;
-    const int64_t S = series->n_segments;
-    if (S == 0) return KRR_OK;
-    if (n_thresholds < 1 || n_thresholds > KRR_MAX_THRESHOLDS)
-        return set_err(ctx, KRR_E_INVALID, "n_thresholds outside 1..KRR_MAX_THRESHOLDS%s: %lld", "", (long long)n_thresholds);
-    if (!thresholds || !out_count || !out_flags)
-        return set_err(ctx, KRR_E_INVALID, "null thresholds or outputs%s", "");
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-    const MaxArgs M = max_args(series, nullptr, out_count, out_flags, nullptr);  // its remap choice
-    const ExceedArgs A{series->values, series->offsets, S,          series->gaps_are_nan, M.remap,
-                       thresholds,     out_above,       out_excess, out_longest,          out_head,
-                       out_tail,       out_last,        out_count,  out_flags};
-    const dim3 grid(grid_for(S)), block(64);
-    const hipStream_t st = (hipStream_t)stream;
-    static_assert(KRR_MAX_THRESHOLDS == 4, "one k_exceed instantiation per threshold count");
-    switch (n_thresholds) {
-        case 1: hipLaunchKernelGGL(k_exceed<1>, grid, block, 0, st, A); break;
-        case 2: hipLaunchKernelGGL(k_exceed<2>, grid, block, 0, st, A); break;
-        case 3: hipLaunchKernelGGL(k_exceed<3>, grid, block, 0, st, A); break;
-        default: hipLaunchKernelGGL(k_exceed<4>, grid, block, 0, st, A); break;
-    }
-    KRR_HIP(ctx, hipGetLastError());
-    return KRR_OK;
+    return series_entry(ctx, series, out_count, out_flags, KRR_OK, [&](const SeriesArgs& H, dim3 grid) -> int {
+        if (n_thresholds < 1 || n_thresholds > KRR_MAX_THRESHOLDS)
+            return set_err(ctx, KRR_E_INVALID, "n_thresholds outside 1..KRR_MAX_THRESHOLDS%s: %lld", "",
+                           (long long)n_thresholds);
+        if (!thresholds || !out_count || !out_flags)
+            return set_err(ctx, KRR_E_INVALID, "null thresholds or outputs%s", "");
+        const ExceedArgs A{H, thresholds, out_above, out_excess, out_longest, out_head, out_tail, out_last};
+        const dim3 block(64);
+        const hipStream_t st = (hipStream_t)stream;
+        static_assert(KRR_MAX_THRESHOLDS == 4, "one k_exceed instantiation per threshold count");
+        switch (n_thresholds) {
+            case 1: hipLaunchKernelGGL(k_exceed<1>, grid, block, 0, st, A); break;
+            case 2: hipLaunchKernelGGL(k_exceed<2>, grid, block, 0, st, A); break;
+            case 3: hipLaunchKernelGGL(k_exceed<3>, grid, block, 0, st, A); break;
+            default: hipLaunchKernelGGL(k_exceed<4>, grid, block, 0, st, A); break;
+        }
+        return KRR_OK;
+    });
 }
 
 int krr_segmented_rollup(krr_ctx* ctx, const krr_series* series, int64_t window, int32_t align,
                          const int64_t* win_offsets, double* out_wmin, double* out_wmax, double* out_wsum,
                          uint32_t* out_wcount, int64_t* out_count, uint32_t* out_flags, void* stream) {
-    if (!ctx) return KRR_E_INVALID;
-    int rc = check_series(ctx, series);
-    if (rc) return rc;
-    if (window < 1 || window > 2147483647ll)
-        return set_err(ctx, KRR_E_INVALID, "window outside 1..2^31-1%s: %lld", "", (long long)window);
-    if (align != KRR_ROLLUP_START && align != KRR_ROLLUP_END)
-        return set_err(ctx, KRR_E_INVALID, "align is neither KRR_ROLLUP_START nor KRR_ROLLUP_END%s: %lld", "",
-                       (long long)align);
-    const int64_t S = series->n_segments;
-    if (S == 0) return KRR_OK;
-    if (!win_offsets || !out_count || !out_flags)
-        return set_err(ctx, KRR_E_INVALID, "null win_offsets or outputs%s", "");
-    DeviceGuard g(ctx->device);
-    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
-    const MaxArgs M = max_args(series, nullptr, out_count, out_flags, nullptr);  // its remap choice
-    const RollupArgs A{series->values, series->offsets, win_offsets, S,        window,     align == KRR_ROLLUP_END,
-                       series->gaps_are_nan, M.remap,   out_wmin,    out_wmax, out_wsum,   out_wcount,
-                       out_count,      out_flags};
-    if (out_wmin || out_wmax) hipLaunchKernelGGL(k_rollup<true>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(k_rollup<false>, dim3(grid_for(S)), dim3(64), 0, (hipStream_t)stream, A);
-    KRR_HIP(ctx, hipGetLastError());
-    return KRR_OK;
+    // a bad window or align is an error of an empty series too
+    const int early =
+        window < 1 || window > 2147483647ll
+            ? set_err(ctx, KRR_E_INVALID, "window outside 1..2^31-1%s: %lld", "", (long long)window)
+        : align != KRR_ROLLUP_START && align != KRR_ROLLUP_END
+            ? set_err(ctx, KRR_E_INVALID, "align is neither KRR_ROLLUP_START nor KRR_ROLLUP_END%s: %lld", "",
+                      (long long)align)
+            : KRR_OK;
+    return series_entry(ctx, series, out_count, out_flags, early, [&](const SeriesArgs& H, dim3 grid) -> int {
+        if (!win_offsets || !out_count || !out_flags)
+            return set_err(ctx, KRR_E_INVALID, "null win_offsets or outputs%s", "");
+        const RollupArgs A{H, win_offsets, window, align == KRR_ROLLUP_END, out_wmin, out_wmax, out_wsum, out_wcount};
+        if (out_wmin || out_wmax) hipLaunchKernelGGL(k_rollup<true>, grid, dim3(64), 0, (hipStream_t)stream, A);
+        else hipLaunchKernelGGL(k_rollup<false>, grid, dim3(64), 0, (hipStream_t)stream, A);
+        return KRR_OK;
+    });
 }
 
 int krr_simple_run(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,

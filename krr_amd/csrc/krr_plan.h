@@ -111,8 +111,9 @@ KRR_HD inline SidePlan plan_side_multi(int64_t L, const PctSet& ps) {
 constexpr uint32_t kSelectLdsFixed = 1536;
 
 // Elements one streaming iteration can append (U double2 per lane, 64 lanes).
+constexpr int kWave = 64;  // lanes of a wavefront
 constexpr int kUnroll = 8;
-constexpr uint32_t kChunkElems = 2u * kUnroll * 64u;
+constexpr uint32_t kChunkElems = 2u * kUnroll * kWave;
 
 // LDS key capacity for a launch whose largest segment keeps tkeep keys.
 // After a compaction at most tstop = cap - kChunkElems/2 keys remain, so half a
