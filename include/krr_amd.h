@@ -286,6 +286,51 @@ int krr_segmented_rollup(krr_ctx* ctx, const krr_series* series, int64_t window,
                          double* out_wsum, uint32_t* out_wcount, int64_t* out_count,
                          uint32_t* out_flags, void* stream);
 
+/* Per object, ONE pass: its pods folded slot by slot into one series — the workload's total over
+ * time (sum by (workload)), the replica count over time and the busiest-pod envelope
+ * (krr_amd.api.FleetOverlay).  `pods` holds one segment per pod, as for krr_simple_run_pods; object
+ * g owns pod segments pod_groups[g] .. pod_groups[g+1] (device, [n_objects + 1]).  With Lp the slots
+ * of pod p and Lg = max Lp over the object's pods (0 without pods) the overlay has Lg slots:
+ *   - KRR_OVERLAY_START: pod slot i falls on object slot i;
+ *   - KRR_OVERLAY_END:   pod slot i falls on object slot i + (Lg - Lp): the pods END together.
+ * A pod does not reach an object slot outside its own [0, Lp) after the shift.  Per object slot, P =
+ * the pods that reach it, in pod order; with gaps_are_nan only those whose sample there is not NaN.
+ *   active = |P|
+ *   sum    = ((+0.0 + x1) + x2) + ... in pod order: plain IEEE, uncompensated, +0.0 when P is
+ *            empty.  ONE fixed order: a loop over the pods reproduces it bit for bit, and the bits
+ *            depend neither on where the object lies in the buffer, nor on the launch, nor on which
+ *            other outputs are NULL.  A NaN sum leaves as the quiet NaN 0x7FF8000000000000
+ *   max, min = the FIRST extremal sample in pod order under float comparison, with its own bits
+ *            (-0.0 == +0.0 and the earlier pod wins, Python's max() / min()); the quiet NaN when P
+ *            is empty
+ *   - a NaN sample that reaches the slot in the compact layout (gaps_are_nan == 0) counts in
+ *     active, makes the slot's sum, max and min the quiet NaN and sets KRR_FLAG_NAN on the object;
+ *   - +-Inf: plain IEEE, no flag; a slot that holds +Inf and -Inf has a NaN sum.
+ * Slot j of object g is written at out_offsets[g] + j of each per-slot output.  out_offsets (device,
+ * [n_objects + 1]) comes from the caller: the exclusive cumulative sum of Lg, or any layout that
+ * leaves every object at least Lg entries.  The kernel derives Lg itself: where
+ * out_offsets[g+1] - out_offsets[g] < Lg it writes NO slot of that object and ORs KRR_FLAG_CAPACITY
+ * into its flags (count and the other flags as otherwise); it never writes outside
+ * [out_offsets[g], out_offsets[g] + Lg).  Each of the four per-slot outputs may be NULL: it is not
+ * written and its arithmetic is skipped.
+ * out_count[g] = the sum of active over the object's slots; out_flags[g] = KRR_FLAG_EMPTY when that
+ * is 0, KRR_FLAG_NAN as above.  Where the pod segments tile an object-level series both equal
+ * krr_segmented_stats' count and flags of that series.
+ * KRR_E_INVALID, while n_objects > 0: a null ctx, pods, pod_groups or out_offsets; a null out_count
+ * or out_flags; an align that is neither value.  n_objects == 0 launches nothing.  Asynchronous, no
+ * synchronisation; pod_groups is not read back: the kernel clamps group bounds into
+ * [0, n_segments] and pod bounds into [0, n_values], so bad offsets read nothing that is not there
+ * (validating them is the caller's business, who holds host copies).
+ * One wave per object, one read of every value; no atomics, no LDS.  Known limit: an object with
+ * very many long pods is a long tail, as a very long segment is for krr_segmented_stats; objects
+ * are not split over waves. */
+#define KRR_OVERLAY_START 0
+#define KRR_OVERLAY_END 1
+int krr_pods_overlay(krr_ctx* ctx, const krr_series* pods, const int64_t* pod_groups, int64_t n_objects,
+                     int32_t align, const int64_t* out_offsets, double* out_sum, double* out_max,
+                     double* out_min, uint32_t* out_active, int64_t* out_count, uint32_t* out_flags,
+                     void* stream);
+
 /* SimpleStrategy.run over every object: cpu and mem each hold one segment per
  * object (same n_segments).  Outputs are device pointers of n_segments entries. */
 int krr_simple_run(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,

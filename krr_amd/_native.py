@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "krr_segmented_moments",
     "krr_segmented_exceed",
     "krr_segmented_rollup",
+    "krr_pods_overlay",
     "krr_simple_run",
     "krr_simple_run_records",
     "krr_simple_run_forward",
@@ -238,6 +239,8 @@ KRR_MAX_PERCENTILES = 4
 KRR_MAX_THRESHOLDS = 4  # krr_segmented_exceed: thresholds per launch
 KRR_ROLLUP_START = 0  # krr_segmented_rollup: windows start with the series (the last may be partial)
 KRR_ROLLUP_END = 1    # ... or end with it (the first may be partial)
+KRR_OVERLAY_START = 0  # krr_pods_overlay: an object's pods start together
+KRR_OVERLAY_END = 1    # ... or end together
 
 
 class KrrMultiPlanInfo(ctypes.Structure):
@@ -306,6 +309,8 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_segmented_exceed.restype = ctypes.c_int
         lib.krr_segmented_rollup.argtypes = [vp, sp, i64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_segmented_rollup.restype = ctypes.c_int
+        lib.krr_pods_overlay.argtypes = [vp, sp, vp, i64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_pods_overlay.restype = ctypes.c_int
         lib.krr_simple_run.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_simple_run_records.restype = ctypes.c_int
@@ -573,6 +578,30 @@ class Context:
         self._check(self._lib.krr_segmented_rollup(
             self._h, ctypes.byref(series), int(window), int(align), win_offsets.data_ptr(),
             *(None if t is None else t.data_ptr() for t in (wmin, wmax, wsum, wcount)),
+            count.data_ptr(), flags.data_ptr(), self._stream(stream)))
+
+    def pods_overlay(self, pods: KrrSeries, pod_groups, n_objects: int, align: int, out_offsets, osum, omax, omin,
+                     active, count, flags, stream=None) -> None:
+        """An object's pods folded slot by slot, from one pass (krr_pods_overlay).  ``pods`` holds one
+        segment per pod and ``pod_groups`` int64 [n_objects + 1] the pods of each object; ``align``:
+        KRR_OVERLAY_START or KRR_OVERLAY_END.  ``out_offsets`` int64 [n_objects + 1] says where each
+        object's slots go in the flat per-slot outputs ``osum`` / ``omax`` / ``omin`` (float64) and
+        ``active`` (int32 storage, read as uint32), which must reach to the largest entry of
+        out_offsets (the caller's business: the kernel writes the longest pod's slots from
+        out_offsets[g] and none where the span to out_offsets[g + 1] is smaller); each is optional
+        (None: not written).  ``count`` int64 [n_objects] and ``flags`` int32 [n_objects] are
+        required."""
+        n_objects = int(n_objects)
+        _check_tensor(pod_groups, "int64", n_objects + 1)
+        _check_tensor(out_offsets, "int64", n_objects + 1)
+        for t, dt in ((osum, "float64"), (omax, "float64"), (omin, "float64"), (active, "int32")):
+            if t is not None:
+                _check_tensor(t, dt)
+        _check_tensor(count, "int64", n_objects)
+        _check_tensor(flags, "int32", n_objects)
+        self._check(self._lib.krr_pods_overlay(
+            self._h, ctypes.byref(pods), pod_groups.data_ptr(), n_objects, int(align), out_offsets.data_ptr(),
+            *(None if t is None else t.data_ptr() for t in (osum, omax, omin, active)),
             count.data_ptr(), flags.data_ptr(), self._stream(stream)))
 
     def simple_run(self, cpu: KrrSeries, mem: KrrSeries, params: KrrPercentileParams, out: dict,

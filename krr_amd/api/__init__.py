@@ -1,8 +1,8 @@
 """Public plugin-author surface: ``krr_amd.api.strategies`` / ``krr_amd.api.models`` (the
 reference's names) and ``FleetBatch``, the fleet statistics a custom strategy's ``run_batch``
 computes on the device (krr_amd.api.batch)."""
-from krr_amd.api.batch import (FleetBatch, FleetExceedance, FleetMoments, FleetProfile, FleetRollup, FleetStats,
-                               allocation_thresholds)
+from krr_amd.api.batch import (FleetBatch, FleetExceedance, FleetMoments, FleetOverlay, FleetProfile, FleetRollup,
+                               FleetStats, allocation_thresholds)
 
-__all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetProfile", "FleetRollup", "FleetStats",
-           "allocation_thresholds"]
+__all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetOverlay", "FleetProfile", "FleetRollup",
+           "FleetStats", "allocation_thresholds"]

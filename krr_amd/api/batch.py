@@ -13,6 +13,7 @@ on the device, one launch per statistic instead of a Python loop per object:
     v = batch.percentile(ResourceType.Memory, "95", mode="sorted_lower")         # float64 [S]
     vs = batch.percentiles(ResourceType.CPU, ["50", "95", "99"], mode="linear")  # float64 [P, S]
     pods = batch.per_pod(ResourceType.CPU)         # a FleetBatch over one segment per pod + .pod_groups
+    ov = batch.overlay(ResourceType.CPU)           # FleetOverlay: an object's pods folded slot by slot
     batch.to_decimal(values, flags)                # list[Decimal]
 
 ``stats`` is one krr_segmented_stats pass (min and max are the first minimal / maximal sample's own
@@ -42,8 +43,8 @@ from krr_amd.core.models.allocations import ResourceType
 from krr_amd.core.packing import PackedFleet, PackedSeries, pack_resource, pod_view
 from krr_amd.utils.prom_decimal import prom_decimal
 
-__all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetProfile", "FleetRollup", "FleetStats",
-           "allocation_thresholds"]
+__all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetOverlay", "FleetProfile", "FleetRollup",
+           "FleetStats", "allocation_thresholds"]
 
 
 @dataclass
@@ -276,7 +277,73 @@ class FleetProfile:
         return out
 
 
-class FleetRollup:
+class _FlatPerObject:
+    """What FleetRollup and FleetOverlay share: flat per-entry tensors where the kernel left them,
+    object s owning entries ``offsets[s] .. offsets[s+1]``; a host copy per stat on first use;
+    ``of`` and ``dense``.  A subclass sets ``offsets``, ``align`` and ``_t`` (the kernel's tensors
+    by stat), names its stats in ``_STATS`` and its per-entry count in ``_COUNT``."""
+    _STATS: tuple = ()
+    _COUNT: str = ""
+
+    @property
+    def n_objects(self) -> int:
+        return self.offsets.size - 1
+
+    @classmethod
+    def _stat(cls, stat: str, allowed=None) -> str:
+        allowed = cls._STATS if allowed is None else allowed
+        if stat not in allowed:
+            raise ValueError(f"unknown stat {stat!r}; expected one of {list(allowed)}")
+        return stat
+
+    def tensor(self, stat: str):
+        """The flat tensor of ``stat`` where the kernel left it (HBM): the count int32, the others
+        float64; ``mean`` is sum / count computed there, NaN where the count is 0."""
+        import torch
+
+        stat = self._stat(stat)
+        t = self._t.get(stat)
+        if t is None:  # mean
+            n = self._t[self._COUNT]
+            t = self._t["mean"] = torch.where(n > 0, self._t["sum"] / n.to(torch.float64),
+                                              torch.full_like(self._t["sum"], float("nan")))
+        return t
+
+    def _flat(self, stat: str) -> np.ndarray:
+        a = self._host.get(stat)
+        if a is None:
+            a = self._host[stat] = self.tensor(stat).cpu().numpy()
+        return a
+
+    def of(self, s: int, stat: str = "mean") -> np.ndarray:
+        """The entries of object ``s``, oldest first."""
+        s = int(s)
+        if not 0 <= s < self.n_objects:
+            raise IndexError(f"object {s} of {self.n_objects}")
+        return self._flat(stat)[self.offsets[s]:self.offsets[s + 1]]
+
+    def _dense_index(self, width: int):
+        """(rows, columns) of every entry in a [S, width] layout: right-justified for
+        ``align="end"`` (the last column is every object's last entry), else left-justified."""
+        nw = np.diff(self.offsets)
+        rows = np.repeat(np.arange(self.n_objects, dtype=np.int64), nw)
+        cols = np.arange(int(self.offsets[-1]), dtype=np.int64) - np.repeat(self.offsets[:-1], nw)
+        if self.align == "end":
+            cols += np.repeat(width - nw, nw)
+        return rows, cols
+
+    def dense(self, stat: str = "mean") -> np.ndarray:
+        """float64 [S, longest object], NaN where an object has no entry: right-justified for
+        ``align="end"``, left-justified for ``"start"``."""
+        flat = self._flat(stat)
+        width = int(np.diff(self.offsets).max()) if self.n_objects else 0
+        out = np.full((self.n_objects, width), np.nan, dtype=np.float64)
+        rows, cols = self._dense_index(width)
+        out[rows, cols] = flat
+        return out
+
+
+class FleetRollup(_FlatPerObject):
     """One resource of a fleet with the time axis coarsened: every object's series cut into
     windows of ``window`` slots, and per window the count, min, max and sum of its present samples
     (one krr_segmented_rollup pass; include/krr_amd.h has the rules).  ``align="end"``: the windows
@@ -294,6 +361,8 @@ class FleetRollup:
     Two rollups of adjacent time slices cannot be merged: a window that straddles the cut would
     need both sides' partial windows, which the window grid of either side does not keep.  There
     is no ``concat``; roll up the joined series instead."""
+    _STATS = _ROLLUP_STATS
+    _COUNT = "wcount"
 
     def __init__(self, resource, window: int, align: str, offsets, slots, count, flags, wcount, wmin, wmax, wsum,
                  device: int = 0, engine: Optional[SimpleEngine] = None):
@@ -319,70 +388,14 @@ class FleetRollup:
         self._batches: dict = {}
 
     @property
-    def n_objects(self) -> int:
-        return self.slots.size
-
-    @property
     def n_windows(self) -> np.ndarray:
         return np.diff(self.offsets)
-
-    @staticmethod
-    def _stat(stat: str, allowed=_ROLLUP_STATS) -> str:
-        if stat not in allowed:
-            raise ValueError(f"unknown stat {stat!r}; expected one of {list(allowed)}")
-        return stat
-
-    def tensor(self, stat: str):
-        """The flat per-window tensor of ``stat`` where the kernel left it (HBM): ``wcount`` int32,
-        the others float64."""
-        import torch
-
-        stat = self._stat(stat)
-        t = self._t.get(stat)
-        if t is None:  # mean
-            n = self._t["wcount"]
-            t = self._t["mean"] = torch.where(n > 0, self._t["sum"] / n.to(torch.float64),
-                                              torch.full_like(self._t["sum"], float("nan")))
-        return t
-
-    def _flat(self, stat: str) -> np.ndarray:
-        a = self._host.get(stat)
-        if a is None:
-            a = self._host[stat] = self.tensor(stat).cpu().numpy()
-        return a
 
     wcount = property(lambda self: self._flat("wcount"), doc="present samples per window (int32, flat, host)")
     min = property(lambda self: self._flat("min"), doc="float64, flat, host")
     max = property(lambda self: self._flat("max"), doc="float64, flat, host")
     sum = property(lambda self: self._flat("sum"), doc="float64, flat, host")
     mean = property(lambda self: self._flat("mean"), doc="sum / wcount, NaN where wcount == 0 (float64, flat, host)")
-
-    def of(self, s: int, stat: str = "mean") -> np.ndarray:
-        """The windows of object ``s``, oldest first."""
-        s = int(s)
-        if not 0 <= s < self.n_objects:
-            raise IndexError(f"object {s} of {self.n_objects}")
-        return self._flat(stat)[self.offsets[s]:self.offsets[s + 1]]
-
-    def _dense_index(self, width: int):
-        """(rows, columns) of every window in a [S, width] layout: right-justified for
-        ``align="end"`` (the last column is every series' last window), else left-justified."""
-        nw = self.n_windows
-        rows = np.repeat(np.arange(self.n_objects, dtype=np.int64), nw)
-        cols = np.arange(int(self.offsets[-1]), dtype=np.int64) - np.repeat(self.offsets[:-1], nw)
-        if self.align == "end":
-            cols += np.repeat(width - nw, nw)
-        return rows, cols
-
-    def dense(self, stat: str = "mean") -> np.ndarray:
-        """float64 [S, max windows], NaN where an object has no window: right-justified for
-        ``align="end"``, left-justified for ``"start"``."""
-        flat = self._flat(stat)
-        width = int(self.n_windows.max()) if self.n_objects else 0
-        out = np.full((self.n_objects, width), np.nan, dtype=np.float64)
-        rows, cols = self._dense_index(width)
-        out[rows, cols] = flat
-        return out
 
     def as_batch(self, stat: str = "mean") -> "FleetBatch":
         """A FleetBatch whose series of this resource is the per-window ``stat`` (``min``, ``max``,
@@ -455,6 +468,101 @@ class FleetRollup:
         mx = torch.where(none | bad, nan, mx)
         total = torch.where(bad, nan, total)
         return FleetProfile(count.cpu().numpy(), mn.cpu().numpy(), mx.cpu().numpy(), total.cpu().numpy())
+
+
+_OVERLAY_ALIGN = {"start": _native.KRR_OVERLAY_START, "end": _native.KRR_OVERLAY_END}
+_OVERLAY_SERIES_STATS = ("sum", "max", "min", "mean")
+_OVERLAY_STATS = ("active",) + _OVERLAY_SERIES_STATS
+
+
+class FleetOverlay(_FlatPerObject):
+    """One resource of a fleet with every object's pods folded slot by slot into ONE series (one
+    krr_pods_overlay pass; include/krr_amd.h has the rules): per slot ``active`` (the pods with a
+    sample there: the replica count), ``sum`` (the workload's total, ``sum by (workload)``),
+    ``max`` / ``min`` (the busiest- / idlest-pod envelope) and ``mean`` (sum / active: the
+    per-replica load if the work were spread evenly).  The sum adds the pods in pod order,
+    ((0 + x1) + x2) + ..., one fixed order with the same bits on every run.
+
+    The slot axis is the pods' own.  On the dense grid (``pack_dense_grid``, the gapped layouts)
+    every pod has the same slots and a slot is a point in wall-clock time.  In the compact layouts
+    a slot is a SAMPLE INDEX: ``align="end"`` lines the pods up at their last sample (pods end
+    "now"), ``"start"`` at their first, and an object has as many slots as its longest pod — the
+    convention ``FleetMoments`` uses for its slot index.
+
+    Object s owns slots ``offsets[s] .. offsets[s+1]`` of the flat per-slot arrays (``offsets``
+    int64 [S + 1], ``slots`` [S] the longest pod, ``pods`` [S] the pods per object, all host).  The
+    per-slot arrays live in HBM; ``active``, ``sum``, ``max``, ``min`` and ``mean`` copy them to
+    the host on first use.  A slot no pod has a sample at has active 0, sum 0 and max = min = mean =
+    NaN.  ``count`` ([S]: the samples folded, the sum of active) and ``flags`` ([S]) are
+    ``FleetBatch.stats``' for the object's whole series."""
+    _STATS = _OVERLAY_STATS
+    _COUNT = "active"
+
+    def __init__(self, resource, align: str, offsets, slots, pods, count, flags, active, osum, omax, omin,
+                 device: int = 0, engine: Optional[SimpleEngine] = None):
+        import torch
+
+        self.resource = ResourceType(resource)
+        self.align = str(align)
+        if self.align not in _OVERLAY_ALIGN:
+            raise ValueError(f"unknown align {align!r}; expected 'start' or 'end'")
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        self.slots = np.asarray(slots, dtype=np.int64)
+        self.pods = np.asarray(pods, dtype=np.int64)
+        self.count = np.asarray(count, dtype=np.int64)
+        self.flags = np.asarray(flags).astype(np.uint32)
+        self.device = int(device)
+        self._engine = engine
+        self._t = {"active": torch.as_tensor(active), "sum": torch.as_tensor(osum), "max": torch.as_tensor(omax),
+                   "min": torch.as_tensor(omin)}
+        n = int(self.offsets[-1]) if self.offsets.size else 0
+        if (self.offsets.size != self.slots.size + 1 or self.pods.size != self.slots.size
+                or any(t.numel() != n for t in self._t.values())):
+            raise ValueError("offsets, slots, pods and the per-slot arrays do not describe the same slots")
+        self._host: dict = {}
+        self._batches: dict = {}
+
+    active = property(lambda self: self._flat("active"), doc="pods with a sample per slot (int32, flat, host)")
+    sum = property(lambda self: self._flat("sum"), doc="float64, flat, host")
+    max = property(lambda self: self._flat("max"), doc="float64, flat, host")
+    min = property(lambda self: self._flat("min"), doc="float64, flat, host")
+    mean = property(lambda self: self._flat("mean"), doc="sum / active, NaN where active == 0 (float64, flat, host)")
+
+    def as_batch(self, stat: str = "sum") -> "FleetBatch":
+        """A FleetBatch whose series of this resource is the per-slot ``stat``, in HBM as it is, one
+        segment per object over ``offsets``.  ``sum``, ``max``, ``min`` and ``mean`` give a gapped
+        series in which a slot with ``active == 0`` is absent; ``active`` gives a compact float64
+        series in which 0 is a value ("no pod up").  ``stats``, ``moments``, ``exceedance``,
+        ``percentiles`` and ``rollup`` apply to it.  Raises ValueError if an object is flagged
+        KRR_FLAG_NAN: its NaN slots would read as absent and the NaN be dropped."""
+        import torch
+
+        stat = self._stat(stat)
+        if (self.flags & _native.KRR_FLAG_NAN).any():
+            s = int(np.flatnonzero(self.flags & _native.KRR_FLAG_NAN)[0])
+            raise ValueError(f"object {s} holds a NaN sample (KRR_FLAG_NAN): as a gapped series its NaN slots "
+                             f"would be dropped silently")
+        batch = self._batches.get(stat)
+        if batch is None:
+            vals = self.tensor(stat)
+            gapped = stat != "active"
+            if stat == "active":
+                vals = vals.to(torch.float64)
+            elif stat == "sum":
+                vals = torch.where(self._t["active"] > 0, vals, torch.full_like(vals, float("nan")))
+            longest = int(self.slots.max()) if self.n_objects else 0
+            if vals.is_cuda:
+                ps = PackedSeries(vals.contiguous(), torch.from_numpy(self.offsets).to(vals.device), longest, gapped)
+            else:
+                ps = PackedSeries(vals.numpy(), self.offsets, longest, gapped)
+            batch = self._batches[stat] = FleetBatch._of({self.resource: ps}, self.n_objects, self.device,
+                                                         self._engine)
+        return batch
+
+    def peak(self, stat: str = "sum") -> np.ndarray:
+        """float64 [S]: the largest slot value of every object — with ``sum`` the workload's peak
+        total, with ``active`` the most replicas at once; NaN without a sample."""
+        return self.as_batch(stat).stats(self.resource).max
 
 
 def allocation_thresholds(objects: Sequence, resource: ResourceType, which: str = "requests") -> np.ndarray:
@@ -627,6 +735,34 @@ class FleetBatch:
                                                 r["flags"], r["wcount"], r["min"], r["max"], r["sum"],
                                                 self.device, self.engine)
         return ru
+
+    def overlay(self, resource: ResourceType, align: str = "end") -> FleetOverlay:
+        """Every object's pods folded slot by slot into one series (FleetOverlay): per slot the
+        pods with a sample (``active``), their ``sum``, ``max`` and ``min``; one krr_pods_overlay
+        pass, cached per (resource, align).  ``align="end"`` (the default) lines an object's pods
+        up at their last slot, ``"start"`` at their first; on the dense grid, where every pod has
+        the same slots, both are wall-clock time.  The result's ``as_batch(stat)`` is a FleetBatch
+        again, so the p95 of a workload's total over hourly means is
+
+            ov = batch.overlay(ResourceType.CPU)
+            ov.as_batch("sum").rollup(ResourceType.CPU, 60).as_batch("mean").percentile(ResourceType.CPU, "95")
+
+        Needs the series' pod boundaries (``per_pod`` says which series carry them): on a
+        ``per_pod()`` view, whose series has none, it raises the same ValueError."""
+        if align not in _OVERLAY_ALIGN:
+            raise ValueError(f"unknown align {align!r}; expected 'start' or 'end'")
+        resource = ResourceType(resource)
+        key = (resource, "overlay", align)
+        ov = self._cache.get(key)
+        if ov is None:
+            r = self.engine.overlay_series(self.series(resource), _OVERLAY_ALIGN[align])
+            if (r["flags"] & _native.KRR_FLAG_CAPACITY).any():
+                s = int(np.flatnonzero(r["flags"] & _native.KRR_FLAG_CAPACITY)[0])
+                raise RuntimeError(f"object {s}: slot offsets too small for its slots (KRR_FLAG_CAPACITY)")
+            ov = self._cache[key] = FleetOverlay(resource, align, r["offsets"], r["slots"], r["pods"], r["count"],
+                                                 r["flags"], r["active"], r["sum"], r["max"], r["min"],
+                                                 self.device, self.engine)
+        return ov
 
     def percentiles(self, resource: ResourceType, percentiles: Sequence, mode: str = "ref_index",
                     return_flags: bool = False):

@@ -422,6 +422,102 @@ class SimpleEngine:
                                  out["count"], out["flags"])
         return out, wo
 
+    def overlay_series(self, ps: PackedSeries, align: int) -> dict:
+        """Every object's pods folded slot by slot (krr_pods_overlay; ``align`` KRR_OVERLAY_START
+        or KRR_OVERLAY_END): ``active`` (int32), ``sum``, ``max``, ``min`` (float64) as flat
+        DEVICE tensors with one entry per object slot — together as large as the series, so they
+        stay in HBM — ``offsets`` (host int64 [S + 1]: object s owns slots offsets[s] ..
+        offsets[s+1]), ``slots`` (its longest pod) and ``pods`` (int64 [S]), ``count`` (int64)
+        and ``flags`` (uint32) as host arrays [S].  The series needs its pod boundaries
+        (``pod_view``'s ValueError names the packers), which are validated on the host: pod_groups
+        spans the pod segments and does not decrease.  Chunks as ``stats_series``: whole objects,
+        the chunks' slots concatenated on the device and their offsets rebased.  The slot offsets
+        of a host series come from its host pod offsets; for a series resident in HBM they are
+        computed there and read back, the one synchronisation before the outputs are sized."""
+        import torch
+
+        from krr_amd.core.packing import pod_view
+
+        if ps.pod_offsets is None or ps.pod_groups is None:
+            pod_view(ps)  # raises the ValueError that names the packers
+        if isinstance(ps.pod_groups, np.ndarray):
+            groups = np.asarray(ps.pod_groups, dtype=np.int64)
+            if groups.size != ps.n_segments + 1 or groups[0] != 0 or groups[-1] != ps.n_pods or (np.diff(groups) < 0).any():
+                raise ValueError(f"pod_groups must run from 0 to the {ps.n_pods} pod segments in {ps.n_segments} + 1 "
+                                 f"non-decreasing entries")
+        ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        dev = torch.device("cuda", self.device)
+        parts, offs, pods, base = [], [np.zeros(1, dtype=np.int64)], [], 0
+        for part in self._series_parts(ps):
+            out, oo, npods = self._overlay_part(ctx, part, align)
+            parts.append(out)
+            offs.append(oo[1:] + base)
+            pods.append(npods)
+            base += int(oo[-1])
+        names = (("active", torch.int32), ("sum", torch.float64), ("max", torch.float64), ("min", torch.float64))
+        if not parts:
+            res = {k: torch.empty(0, dtype=dt, device=dev) for k, dt in names}
+        elif len(parts) == 1:
+            res = {k: parts[0][k] for k, _ in names}
+        else:
+            res = {k: torch.cat([p[k] for p in parts]) for k, _ in names}
+        host = self._host_concat([{k: p[k] for k in ("count", "flags")} for p in parts],
+                                 {"count": np.int64, "flags": np.int32})
+        offsets = np.concatenate(offs)
+        res.update(offsets=offsets, slots=np.diff(offsets),
+                   pods=np.concatenate(pods) if pods else np.zeros(0, dtype=np.int64),
+                   count=host["count"], flags=host["flags"])
+        return res
+
+    def _overlay_part(self, ctx, part: PackedSeries, align: int) -> tuple:
+        """Upload (host series) and one krr_pods_overlay launch on the current stream: the chunk's
+        device tensors, its slot offsets and its pods per object as host arrays."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n = part.n_segments
+        with torch.cuda.device(self.device):
+            if isinstance(part.pod_groups, np.ndarray):
+                po = np.ascontiguousarray(part.pod_offsets, dtype=np.int64)
+                groups = np.ascontiguousarray(part.pod_groups, dtype=np.int64)
+                npods = np.diff(groups)
+                lg = np.zeros(n, dtype=np.int64)
+                np.maximum.at(lg, np.repeat(np.arange(n, dtype=np.int64), npods), np.diff(po))
+                oo = np.zeros(n + 1, dtype=np.int64)
+                np.cumsum(lg, out=oo[1:])
+                vals, _ = self._to_device(part)
+                d_po, d_groups, d_oo = (torch.from_numpy(a).to(dev) for a in (po, groups, oo))
+                longest = int(lg.max(initial=0))
+            else:
+                vals, _ = self._to_device(part)
+                d_po, d_groups = part.pod_offsets.contiguous(), part.pod_groups.contiguous()
+                if d_po.device != dev or d_groups.device != dev:
+                    raise ValueError(f"pod boundaries on {d_po.device}, engine runs on {dev}: pack on the engine's device")
+                n_pods = d_po.numel() - 1
+                if d_groups.numel() != n + 1:
+                    raise ValueError(f"pod_groups holds {d_groups.numel()} entries for {n} objects")
+                per = d_groups[1:] - d_groups[:-1]
+                ok = (d_groups[0] == 0) & (d_groups[-1] == n_pods) & (per >= 0).all()
+                owner = torch.searchsorted(d_groups[1:].contiguous(), torch.arange(n_pods, device=dev), right=True)
+                lg = torch.zeros(n, dtype=torch.int64, device=dev)
+                if n_pods > 0:
+                    lg.scatter_reduce_(0, owner.clamp_(0, max(n - 1, 0)), d_po[1:] - d_po[:-1], "amax")
+                d_oo = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+                torch.cumsum(lg, 0, out=d_oo[1:])
+                back = torch.cat([d_oo, per, ok.to(torch.int64).reshape(1)]).cpu().numpy()  # the one synchronisation
+                if not back[-1]:
+                    raise ValueError(f"pod_groups must run from 0 to the {n_pods} pod segments in {n} + 1 "
+                                     f"non-decreasing entries")
+                oo, npods = back[:n + 1], back[n + 1:2 * n + 1]
+                longest = int(np.diff(oo).max(initial=0))
+            series = ctx.series(vals, d_po, max(longest, 1), part.gaps_are_nan)
+            out = {**self._outputs((("active", torch.int32, 0), ("sum", torch.float64, 0), ("max", torch.float64, 0),
+                                     ("min", torch.float64, 0)), int(oo[-1])),
+                   **self._outputs((("count", torch.int64, 0), ("flags", torch.int32, 0)), n)}
+            ctx.pods_overlay(series, d_groups, n, align, d_oo, out["sum"], out["max"], out["min"], out["active"],
+                             out["count"], out["flags"])
+        return out, oo, npods
+
     def percentiles_series(self, ps: PackedSeries, params_list) -> tuple:
         """Several percentiles of every segment of one series — CPU or memory — through
         krr_segmented_percentiles: (value float64 [P, S], count int64 [S], flags uint32 [P, S]),

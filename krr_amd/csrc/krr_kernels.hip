@@ -3964,6 +3964,156 @@ __global__ __launch_bounds__(64) void k_rollup(RollupArgs A) {
     }
 }
 
+// ------------------------------ OVERLAY ------------------------------------
+// krr_pods_overlay: an object's pods folded slot by slot (include/krr_amd.h has the rules).  One
+// wave per object, no LDS, no atomics.  The lanes lie along the object's slot axis and every lane
+// walks the pods in pod order, so a wave load is a contiguous run of ONE pod (coalesced whatever
+// the pod's start parity or END shift) and the sum of a slot is ((+0.0 + x1) + x2) + ... in one
+// fixed order.  A tile is ROWS rows of 64 slots; per tile the pods come PODS at a time, their
+// ROWS x PODS 8-byte loads issued before the first is used.  An object with one pod takes tiles of
+// 16 rows and no accumulators (ONE), objects with more 8 rows x 2 pods: 16 loads in flight per
+// lane either way.  A lane whose slot a pod does not reach issues no load for it.
+constexpr int kOvRowsOne = 16, kOvRows = 8, kOvPods = 2;
+
+struct OverlayArgs {
+    const double* vals;
+    int64_t n_values;
+    const int64_t* poffs;  // [n_pods + 1]
+    int64_t n_pods;
+    const int64_t* groups;  // [G + 1]
+    int64_t G;
+    int32_t gaps;
+    int32_t align_end;
+    const int64_t* ooffs;  // [G + 1]
+    double* out_sum;       // the four per-slot outputs may each be null
+    double* out_max;
+    double* out_min;
+    uint32_t* out_act;
+    int64_t* out_n;
+    uint32_t* out_f;
+};
+
+__device__ __forceinline__ int64_t clamp_i64(int64_t x, int64_t lo, int64_t hi) {
+    return x < lo ? lo : x > hi ? hi : x;
+}
+
+// Pod p's values as [beg, beg + len), clamped into [0, n_values].
+struct OvPod {
+    int64_t beg, len;
+};
+__device__ __forceinline__ OvPod overlay_pod(const OverlayArgs& A, int64_t p) {
+    const int64_t b = clamp_i64(A.poffs[p], 0, A.n_values);
+    const int64_t e = clamp_i64(A.poffs[p + 1], b, A.n_values);
+    return OvPod{b, e - b};
+}
+
+// Slots [j0, j0 + ROWS * 64) of the object with pods [p0, p1) and Lg slots: lane l holds slots
+// j0 + r * 64 + l.  Returns this lane's active count; `bad` collects its NaN samples (compact).
+template <bool SM, bool MM, int ROWS, int PODS, bool ONE>
+__device__ __forceinline__ uint32_t overlay_tile(const OverlayArgs& A, int64_t p0, int64_t p1, int64_t Lg, int64_t j0,
+                                                 int64_t obeg, bool fits, int lane, bool& bad) {
+    double sm[ROWS], mx[ROWS], mn[ROWS];
+    uint32_t act[ROWS];
+    bool nan[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        sm[r] = 0.0;
+        mx[r] = mn[r] = bitsd(kQuietNaN);
+        act[r] = 0u;
+        nan[r] = false;
+    }
+    const int64_t jl = j0 + lane;
+    const bool gaps = A.gaps != 0;
+    for (int64_t p = p0; p < (ONE ? p0 + 1 : p1); p += PODS) {
+        double x[PODS][ROWS];
+        bool in[PODS][ROWS];
+#pragma unroll
+        for (int q = 0; q < PODS; ++q) {
+            const bool live = ONE || q == 0 || p + q < p1;  // uniform
+            const OvPod pod = live ? overlay_pod(A, p + q) : OvPod{0, 0};
+            const int64_t shift = A.align_end ? Lg - pod.len : 0;
+            const double* __restrict__ src = A.vals + pod.beg;
+            const int64_t i0 = jl - shift;  // the pod slot that falls on this lane's slot of row 0
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const int64_t i = i0 + r * kWave;
+                in[q][r] = (uint64_t)i < (uint64_t)pod.len;  // 0 <= i < len
+                x[q][r] = bitsd(kQuietNaN);
+                if (in[q][r]) x[q][r] = __builtin_nontemporal_load(src + i);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < PODS; ++q) {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const double v = x[q][r];
+                const bool isn = __builtin_isnan(v);
+                const bool cnt = in[q][r] && !(gaps && isn);  // the pod is in P at this slot
+                act[r] += cnt ? 1u : 0u;
+                nan[r] |= cnt && isn;
+                // !(v <= mx): v > mx, or mx still the NaN of an empty P; the earlier pod keeps a tie
+                if constexpr (SM) sm[r] = cnt ? sm[r] + v : sm[r];
+                if constexpr (MM) {
+                    mx[r] = cnt && !(v <= mx[r]) ? v : mx[r];
+                    mn[r] = cnt && !(v >= mn[r]) ? v : mn[r];
+                }
+            }
+        }
+    }
+    uint32_t total = 0u;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        const int64_t j = jl + r * kWave;
+        total += act[r];
+        bad |= nan[r];
+        if (fits && j < Lg) {
+            const int64_t o = obeg + j;
+            // a NaN sum (a NaN sample, or +Inf with -Inf) leaves as the one quiet NaN
+            if constexpr (SM)
+                if (A.out_sum) A.out_sum[o] = nan[r] || __builtin_isnan(sm[r]) ? bitsd(kQuietNaN) : sm[r];
+            if constexpr (MM) {
+                if (A.out_max) A.out_max[o] = nan[r] ? bitsd(kQuietNaN) : mx[r];
+                if (A.out_min) A.out_min[o] = nan[r] ? bitsd(kQuietNaN) : mn[r];
+            }
+            if (A.out_act) A.out_act[o] = act[r];
+        }
+    }
+    return total;
+}
+
+template <bool SM, bool MM>
+__global__ __launch_bounds__(64) void k_overlay(OverlayArgs A) {
+    const int lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < A.G; b += gridDim.x) {
+        const int64_t g = xcd_item(b, A.G, 1);
+        const int64_t p0 = clamp_i64(A.groups[g], 0, A.n_pods);
+        const int64_t p1 = clamp_i64(A.groups[g + 1], p0, A.n_pods);
+        const int64_t obeg = A.ooffs[g], oend = A.ooffs[g + 1];
+        int64_t mine = 0;  // the longest of this lane's pods
+        for (int64_t p = p0 + lane; p < p1; p += kWave) {
+            const int64_t len = overlay_pod(A, p).len;
+            mine = len > mine ? len : mine;
+        }
+        const int64_t Lg = (int64_t)wave_max_u64((uint64_t)mine);
+        const bool fits = oend - obeg >= Lg;
+        uint64_t n = 0;
+        bool bad = false;
+        if (p1 - p0 == 1) {
+            for (int64_t j0 = 0; j0 < Lg; j0 += kOvRowsOne * kWave)
+                n += overlay_tile<SM, MM, kOvRowsOne, 1, true>(A, p0, p1, Lg, j0, obeg, fits, lane, bad);
+        } else {
+            for (int64_t j0 = 0; j0 < Lg; j0 += kOvRows * kWave)
+                n += overlay_tile<SM, MM, kOvRows, kOvPods, false>(A, p0, p1, Lg, j0, obeg, fits, lane, bad);
+        }
+        const uint64_t count = wave_sum_u64(n);
+        const bool any_nan = ballot(bad) != 0;
+        if (lane == 0) {
+            A.out_n[g] = (int64_t)count;
+            A.out_f[g] = (count == 0 ? KRR_FLAG_EMPTY : any_nan ? KRR_FLAG_NAN : 0u) | (fits ? 0u : KRR_FLAG_CAPACITY);
+        }
+    }
+}
+
 }  // namespace krr
 #include "krr_kll.h"
 namespace krr {
@@ -4771,6 +4921,35 @@ int krr_segmented_rollup(krr_ctx* ctx, const krr_series* series, int64_t window,
         else hipLaunchKernelGGL(k_rollup<false>, grid, dim3(64), 0, (hipStream_t)stream, A);
         return KRR_OK;
     });
+}
+
+int krr_pods_overlay(krr_ctx* ctx, const krr_series* pods, const int64_t* pod_groups, int64_t n_objects,
+                     int32_t align, const int64_t* out_offsets, double* out_sum, double* out_max, double* out_min,
+                     uint32_t* out_active, int64_t* out_count, uint32_t* out_flags, void* stream) {
+    if (n_objects == 0) return KRR_OK;
+    if (!ctx) return KRR_E_INVALID;
+    if (n_objects < 0) return set_err(ctx, KRR_E_INVALID, "negative n_objects%s: %lld", "", (long long)n_objects);
+    const int rc = check_series(ctx, pods);
+    if (rc) return rc;
+    if (!pod_groups || !out_offsets || !out_count || !out_flags)
+        return set_err(ctx, KRR_E_INVALID, "null pod_groups, out_offsets or outputs%s", "");
+    if (align != KRR_OVERLAY_START && align != KRR_OVERLAY_END)
+        return set_err(ctx, KRR_E_INVALID, "align is neither KRR_OVERLAY_START nor KRR_OVERLAY_END%s: %lld", "",
+                       (long long)align);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    const OverlayArgs A{pods->values, pods->n_values > 0 ? pods->n_values : 0, pods->offsets, pods->n_segments,
+                        pod_groups, n_objects, pods->gaps_are_nan, align == KRR_OVERLAY_END, out_offsets,
+                        out_sum, out_max, out_min, out_active, out_count, out_flags};
+    const dim3 grid(grid_for(n_objects)), block(64);
+    const hipStream_t st = (hipStream_t)stream;
+    const bool mm = out_max || out_min;
+    if (out_sum && mm) hipLaunchKernelGGL((k_overlay<true, true>), grid, block, 0, st, A);
+    else if (out_sum) hipLaunchKernelGGL((k_overlay<true, false>), grid, block, 0, st, A);
+    else if (mm) hipLaunchKernelGGL((k_overlay<false, true>), grid, block, 0, st, A);
+    else hipLaunchKernelGGL((k_overlay<false, false>), grid, block, 0, st, A);
+    KRR_HIP(ctx, hipGetLastError());
+    return KRR_OK;
 }
 
 int krr_simple_run(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,
