@@ -15,11 +15,15 @@ import json
 import math
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 from krr_amd.core.prom_native import PrometheusResponseError, pack_query_range_bodies
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _json_numbers  # noqa: E402  (the corpus tests/test_gpu_json_lattice.py runs on the device)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 JSON_OK, JSON_DROPPED, JSON_HOST = 0, 1, 2
@@ -39,9 +43,7 @@ def lib(tmp_path_factory):
 
 
 def go_format(x: float) -> str:
-    from krr_amd.utils.prom_decimal import prom_format
-
-    return prom_format(x)
+    return _json_numbers.go_format(x)
 
 
 def _value(lib, s: str):
@@ -55,19 +57,8 @@ def _bits(x: float) -> int:
 
 
 def test_shortest_repr_values_of_every_magnitude(lib):
-    rng = np.random.default_rng(7)
-    xs = np.concatenate([
-        rng.gamma(2.0, 0.05, 20000),
-        np.floor(rng.normal(2e8, 2e7, 5000)),
-        np.exp(rng.uniform(-744, 709, 20000)),                       # every exponent, subnormals included
-        rng.integers(0, 2**63, 2000).astype(np.float64) * 2.0 ** rng.integers(0, 900, 2000),
-        np.array([5e-324, 2.2250738585072014e-308, 2.2250738585072009e-308, 1.7976931348623157e308, 0.0, 1.0,
-                  0.1, 0.2, 0.3, 1e22, 1e23, 9007199254740993.0, 123456789012345678.0]),
-    ])
-    xs = np.concatenate([xs, -xs[:3000]])
     bad = []
-    for x in xs:
-        s = go_format(float(x))
+    for s in _json_numbers.shortest_repr_values():
         rc, v = _value(lib, s)
         if rc != 0 or _bits(v) != _bits(float(s)):
             bad.append((s, rc, v))
@@ -78,31 +69,25 @@ def test_random_significands_near_midpoints(lib):
     """1-19 digit significands with exponents over the whole range, plus decimal strings
     built from exact binary midpoints (the halfway cases the round-to-even branch
     decides) — against float(), correctly rounded."""
-    from decimal import Decimal
-
-    rng = np.random.default_rng(11)
-    cases = []
-    for _ in range(40000):
-        nd = int(rng.integers(1, 20))
-        digits = str(int(rng.integers(1, 10))) + "".join(str(int(d)) for d in rng.integers(0, 10, nd - 1))
-        e = int(rng.integers(-360, 320))
-        cases.append(f"{digits}e{e}")
-        cases.append(f"0.{digits}")
-    for _ in range(6000):  # midpoints between adjacent doubles, written exactly when short enough
-        x = float(np.exp(rng.uniform(-50, 50)))
-        lo = Decimal(x)
-        hi = Decimal(float(np.nextafter(x, np.inf)))
-        mid = (lo + hi) / 2
-        s = format(mid, "f")
-        if len(s.replace(".", "").lstrip("0")) <= 19:
-            cases.append(s)
     bad = []
-    for s in cases:
+    for s in _json_numbers.midpoint_cases():
         rc, v = _value(lib, s)
         if rc == 0 and _bits(v) != _bits(float(s)):
             bad.append((s, v, float(s)))
         if rc != 0 and len(s.replace(".", "").replace("-", "").lstrip("0").split("e")[0]) <= 19:
             bad.append((s, "host"))
+    assert not bad, bad[:5]
+
+
+def test_constructed_values_and_timestamps(lib):
+    """The corpus' constructed group (second multiply, halfway cases of every q in [-4, 23],
+    subnormal / underflow / overflow edges, spellings) and its timestamp literals: accepted,
+    with float()'s bits."""
+    bad = []
+    for s in _json_numbers.constructed_values() + _json_numbers.TIMESTAMPS:
+        rc, v = _value(lib, s)
+        if rc != 0 or _bits(v) != _json_numbers.want_bits(s):
+            bad.append((s, rc, v))
     assert not bad, bad[:5]
 
 
@@ -119,8 +104,7 @@ def test_special_spellings(lib, s, want):
     assert _bits(pack_query_range_bodies([[b]]).values[0]) == want
 
 
-@pytest.mark.parametrize("s", ["nan", "inf", "Infinity", ".5", "5.", "1e", "1e+", "--1", "+-1", "1.2.3", "0x10",
-                               "12345678901234567890123", "1" * 25 + ".5", "1e1234567", " 1", "1 ", ""])
+@pytest.mark.parametrize("s", _json_numbers.HANDOVER)
 def test_other_spellings_go_to_the_host(lib, s):
     rc, _ = _value(lib, s)
     assert rc != 0
