@@ -718,16 +718,25 @@ int krr_sketch_refine(krr_ctx* ctx, const krr_series* collected, const krr_sketc
  * Nothing statistical is trusted: a hit is decided by exact counts. */
 #define KRR_FLAG_WINDOW_MISS 16u  /* krr_window_merge: the needed ranks are not inside the
                                      ranks' common window (value NaN): finish it elsewhere */
-#define KRR_WIN_FAIL 0x100u       /* krr_window_hdr.flags: no usable window (keys crowded the LDS) */
-#define KRR_WIN_POINT 0x200u      /* the window is one key (lo == hi): cnt copies of it, no keys stored */
+#define KRR_WIN_FAIL 0x100u       /* krr_window_hdr.flags: no usable window (keys crowded the LDS, or
+                                     the row is too short for the ranks).  Only `flags` is meaningful
+                                     then: lo, hi, below, n and cnt are whatever the stream had
+                                     counted when it stopped, the row is not written, and
+                                     KRR_FLAG_NAN is not reported */
+#define KRR_WIN_POINT 0x200u      /* the window is one key (lo == hi): cnt copies of it, no keys stored
+                                     (cnt may exceed key_cap).  Also how a row ends that copies of
+                                     repeated keys would crowd although key_cap holds the ranks
+                                     asked for: the key at the slice's own rank */
 
 typedef struct {
     uint64_t lo, hi;   /* inclusive key window */
     int64_t below;     /* present samples of the slice with key < lo */
     int64_t n;         /* present samples of the slice (compact layout: every slot) */
     uint32_t cnt;      /* samples with key in [lo, hi]: the first cnt keys of the row */
-    uint32_t flags;    /* KRR_WIN_FAIL, KRR_WIN_POINT, KRR_FLAG_NAN (compact layout) */
-} krr_window_hdr;      /* 40 bytes */
+    uint32_t flags;    /* KRR_WIN_FAIL, KRR_WIN_POINT, KRR_FLAG_NAN (compact layout: the slice holds a
+                          NaN sample; then n is its slot count, cnt is 0 and nothing else is promised) */
+} krr_window_hdr;      /* 40 bytes.  Without KRR_WIN_FAIL, below, n, cnt and the row are exact counts
+                          of the slice against [lo, hi], whichever window the export chose */
 
 /* Keys per row for slices of up to max_slice_len slots with ext_slots slots elsewhere
  * (host only; 0 for REF_INDEX or invalid arguments). */
@@ -738,7 +747,10 @@ int krr_window_export(krr_ctx* ctx, const krr_series* slices, const krr_percenti
 /* n_series series, each with n_slices slices in time order: slice j of series i has
  * header hdr[j * slice_stride + i] and keys keys[(j * slice_stride + i) * key_cap ...].
  * Writes out_value / out_count / out_flags[n_series]; *miss_count (device uint32, may
- * be NULL) is zeroed on the stream, then counts the KRR_FLAG_WINDOW_MISS series. */
+ * be NULL) is zeroed on the stream, then counts the KRR_FLAG_WINDOW_MISS series.
+ * out_count of a KRR_FLAG_WINDOW_MISS series is not defined until the caller has finished the
+ * series: it sums the headers' n, and a KRR_WIN_FAIL header's n means nothing (a failed gapped
+ * slice reports its slot count). */
 int krr_window_merge(krr_ctx* ctx, int64_t n_series, int32_t n_slices, int64_t slice_stride,
                      const krr_window_hdr* hdr, const uint64_t* keys, int64_t key_cap,
                      const krr_percentile_params* params, double* out_value, int64_t* out_count,

@@ -2062,6 +2062,29 @@ struct WindowProc {
         }
         filter_window(nl, nh);
         set_window(nl, nh);
+        // The kept ranks fit the row (krr_window_key_cap holds them with room), yet copies of the
+        // keys at those ranks can crowd it: a side left open (p100: hi stays +inf) over one
+        // repeated key, or a few heavily repeated keys around the rank.  Then the window closes
+        // on the ONE key at the slice's own rank, counted and not stored: exact as any window,
+        // and the merge's counts decide whether the target is that key.  Only a row too short
+        // for the ranks themselves fails.
+        if (cnt > key_cap && ihi - ilo + 1 <= (int64_t)key_cap) {
+            const int64_t last2 = (int64_t)cnt - 1;
+            int64_t ic = (int64_t)floor(c) - (int64_t)below_total();
+            ic = ic < 0 ? 0 : (ic > last2 ? last2 : ic);
+            sp.cnt = cnt;
+            sp.bad = 0;
+            uint64_t mn2, mx2;
+            sp.buf_minmax(mn2, mx2);
+            const uint64_t v = mn2 == mx2 ? mn2 : sp.kth_largest((uint32_t)(cnt - ic), mn2, mx2);
+            __syncthreads();
+            if (sp.bad) {
+                fail = 1;
+                return;
+            }
+            filter_window(v, v);
+            set_window(v, v);
+        }
     }
 };
 
@@ -2266,6 +2289,8 @@ __device__ __forceinline__ void window_export_segment(const WindowExportArgs& X,
     const bool has_nan = nnan && !A.gaps;
     if (!W.fail && n > 0 && !has_nan) W.export_shrink(X.key_cap);
     uint32_t flags = 0;
+    // a NaN sample (compact layout) decides the series by itself: no window, no keys, no failure
+    if (has_nan) W.cnt = 0;
     if (W.fail || (!W.point && W.cnt > X.key_cap)) flags |= KRR_WIN_FAIL;
     if (has_nan) flags |= KRR_FLAG_NAN;
     if (W.point) flags |= KRR_WIN_POINT;

@@ -7,12 +7,17 @@ rows are stacked slice-major (what the all-to-all delivers to the owner) and mer
 (krr_window_merge).  Results are checked bit for bit against the C oracle
 (oracle/krr_oracle.c) on the whole series; a miss must be flagged, never wrong, and the
 regather fallback (krr_amd.core.sketch.finish_window_misses) makes it exact."""
+import os
+import sys
 import zlib
 
 import numpy as np
 import pytest
 
 from oracle import oracle
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _window_model  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -40,9 +45,13 @@ def _same(got, want, mode):
     return ok
 
 
-def _emulate(ctx, x, W, params, gaps, key_cap=None):
+SENT_I = -777  # headers and key rows start as this (tests/_window_model.py: no sample's key)
+
+
+def _emulate(ctx, x, W, params, gaps, key_cap=None, detail=None):
     """x: [S, L] (NaN = gap when gaps).  Export every slice, merge.  Returns value, count,
-    flags, misses (host arrays / int)."""
+    flags, misses, headers (host arrays / int); detail (a dict) also takes the key rows, key_cap
+    and the slices' column cuts."""
     import torch
 
     from krr_amd import _native
@@ -51,8 +60,8 @@ def _emulate(ctx, x, W, params, gaps, key_cap=None):
     cuts = np.array_split(np.arange(L), W)
     kc = key_cap or _native.window_key_cap(max(c.size for c in cuts), L - min(c.size for c in cuts), params)
     dev = torch.device("cuda:0")
-    hdr = torch.empty((W * S, _native.HDR_WORDS), dtype=torch.int64, device=dev)
-    keys = torch.empty((W * S, kc), dtype=torch.int64, device=dev)
+    hdr = torch.full((W * S, _native.HDR_WORDS), SENT_I, dtype=torch.int64, device=dev)
+    keys = torch.full((W * S, kc), SENT_I, dtype=torch.int64, device=dev)
     keep = []
     for j, c in enumerate(cuts):
         xs = _dev(np.ascontiguousarray(x[:, c]).ravel())
@@ -66,6 +75,8 @@ def _emulate(ctx, x, W, params, gaps, key_cap=None):
     miss = torch.zeros(1, dtype=torch.int32, device=dev)
     ctx.window_merge(S, W, S, hdr, keys, kc, params, v, n, f, miss)
     torch.cuda.synchronize()
+    if detail is not None:
+        detail.update(keys=keys.cpu().numpy(), key_cap=kc, cuts=cuts)
     return v.cpu().numpy(), n.cpu().numpy(), f.cpu().numpy().astype(np.uint32), int(miss.item()), hdr.cpu().numpy()
 
 
@@ -104,7 +115,17 @@ def test_window_emulated_ranks(ctx, gaps, mode, pct, W):
         x[7, : L // 2] = np.nan   # empty in the first slices
         x[8] = np.nan             # empty series
     params = percentile_params(Decimal(pct), mode)
-    v, n, f, misses, hdr = _emulate(ctx, x, W, params, gaps)
+    exported = {}
+    v, n, f, misses, hdr = _emulate(ctx, x, W, params, gaps, detail=exported)
+    # every header and row keeps the promise of krr_window_hdr: exact counts against [lo, hi]
+    broken = []
+    for j, c in enumerate(exported["cuts"]):
+        for i in range(S):
+            r = j * S + i
+            viol = _window_model.check_header(x[i, c], gaps, hdr[r], exported["keys"][r], exported["key_cap"], SENT_I)
+            if viol:
+                broken.append((f"series {i} slice {j}", viol, _window_model.unpack_header(hdr[r])))
+    assert not broken, broken[:4]
     ov, on, of = oracle.percentile(x.ravel(), (np.arange(S + 1) * L).astype(np.int64), params.mode, params.p_num,
                                    params.p_den, params.q, gaps)
     is_miss = (f & _native.KRR_FLAG_WINDOW_MISS) != 0
