@@ -331,6 +331,52 @@ int krr_pods_overlay(krr_ctx* ctx, const krr_series* pods, const int64_t* pod_gr
                      double* out_min, uint32_t* out_active, int64_t* out_count, uint32_t* out_flags,
                      void* stream);
 
+/* Per segment, the exact WEIGHTED percentile under a weight that depends on a sample's age: the
+ * recency-weighted quantile (krr_amd.api.FleetBatch.weighted_percentile; a decaying weight is
+ * what Kubernetes VPA's histogram applies).  All pointers are device pointers; age_weights holds
+ * n_weights integers, the outputs n_segments entries each.
+ * Age and weight.  For segment s with L = offsets[s+1] - offsets[s] slots, slot i has age
+ *   a = L - 1 - i            (the LAST slot is "now", age 0)
+ * and weight
+ *   w = age_weights[min(a, n_weights - 1)]:
+ * anything older than the table takes the table's last weight.  Weights are integers so that
+ * every sum is exact and independent of order.  Every weight is <= 2^32 and a segment has fewer
+ * than 2^31 slots, so a segment's total weight stays below 2^63.  The kernel does NOT validate
+ * the table (the Python wrapper does); a larger entry makes the sums wrap, nothing else.  On a
+ * compact layout age is a sample index, not a time: a series that ended early is not shifted
+ * (the same caveat as krr_pods_overlay's KRR_OVERLAY_END).
+ * Present samples and total weight.  P = the present slots: every slot, or the non-NaN slots when
+ * gaps_are_nan; W = sum_P w.  Samples are ordered by the kernels' total order on keys (okey):
+ * -0.0 comes before +0.0, and +-Inf are ordinary values.
+ * The answer.  p = p_num / p_den percent, 0 < p <= 100 and p_den <= 10^15 as in
+ * krr_percentile_params.  With C(v) = the summed weight of the present samples whose key is <= the
+ * key of v, the answer is the smallest present sample v, with its own bits, such that
+ *   C(v) * (100 * p_den) >= W * p_num,
+ * compared in exact 128-bit integers (a product compare: nothing is divided).  This is the
+ * weighted "inverted CDF" quantile; a zero-weight sample is present but can never be the answer.
+ * With unit weights (age_weights = {1}) it is sorted(x)[ceil(n p / 100) - 1].
+ *   - out_wsum[s] = W;
+ *   - out_count, out_flags: bit-identical to krr_segmented_stats on the same series;
+ *   - W == 0 (empty, all absent, or all weights zero): the value is the quiet NaN
+ *     0x7FF8000000000000.  No extra flag: the caller reads out_wsum;
+ *   - KRR_FLAG_NAN (a NaN sample in the compact layout): the value is the quiet NaN, wsum 0;
+ *   - out_passes[s] = how many times the segment's values were streamed: 1 when the first pass
+ *     settles it (W == 0, a flag, or one distinct positive-weight key), at most 9 (one totals pass,
+ *     at most ceil(64 / 10) histogram passes, one collect pass);
+ *   - out_passes and out_wsum may be NULL and are then not written; out_value, out_count and
+ *     out_flags are required.
+ * Determinism.  Every accumulation is an integer sum: the same samples and the same table give
+ * the same bits at ANY start offset, on any launch and in any accumulation order.  That is stronger
+ * than krr_segmented_stats' float sum, whose last bits may depend on the parity of the offset.
+ * KRR_E_INVALID, while n_segments > 0: a null ctx or series; age_weights NULL; n_weights < 1;
+ * p_num <= 0; p_den <= 0; p_num > 100 * p_den; p_den > 10^15; out_value, out_count or out_flags
+ * NULL.  n_segments == 0 launches nothing.  Asynchronous, no synchronisation.
+ * One wave per segment, 20 KiB of LDS per wave (LDS atomics on integers only). */
+int krr_segmented_wquantile(krr_ctx* ctx, const krr_series* series, const uint64_t* age_weights,
+                            int64_t n_weights, int64_t p_num, int64_t p_den, double* out_value,
+                            uint64_t* out_wsum, uint32_t* out_passes, int64_t* out_count,
+                            uint32_t* out_flags, void* stream);
+
 /* SimpleStrategy.run over every object: cpu and mem each hold one segment per
  * object (same n_segments).  Outputs are device pointers of n_segments entries. */
 int krr_simple_run(krr_ctx* ctx, const krr_series* cpu, const krr_series* mem,

@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "krr_segmented_stats",
     "krr_segmented_moments",
     "krr_segmented_exceed",
+    "krr_segmented_wquantile",
     "krr_segmented_rollup",
     "krr_pods_overlay",
     "krr_simple_run",
@@ -307,6 +308,8 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_segmented_moments.restype = ctypes.c_int
         lib.krr_segmented_exceed.argtypes = [vp, sp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_segmented_exceed.restype = ctypes.c_int
+        lib.krr_segmented_wquantile.argtypes = [vp, sp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
+        lib.krr_segmented_wquantile.restype = ctypes.c_int
         lib.krr_segmented_rollup.argtypes = [vp, sp, i64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_segmented_rollup.restype = ctypes.c_int
         lib.krr_pods_overlay.argtypes = [vp, sp, vp, i64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -557,6 +560,29 @@ class Context:
         self._check(self._lib.krr_segmented_exceed(
             self._h, ctypes.byref(series), thresholds.data_ptr(), n_thresholds,
             *(None if t is None else t.data_ptr() for t in (above, excess, longest, head, tail, last)),
+            count.data_ptr(), flags.data_ptr(), self._stream(stream)))
+
+    def segmented_wquantile(self, series: KrrSeries, age_weights, p_num: int, p_den: int, value, wsum, passes,
+                            count, flags, stream=None) -> None:
+        """Per segment the exact weighted percentile ``p_num / p_den`` percent under the
+        age-indexed integer weights ``age_weights`` (krr_segmented_wquantile): int64 storage read
+        as uint64, entry a the weight of the slot a places before the segment's last one, the last
+        entry standing for everything older.  ``value`` float64 [S], ``count`` int64 [S] and
+        ``flags`` int32 [S] are required; ``wsum`` (int64 storage, read as uint64: the total
+        weight of the present samples) and ``passes`` (int32 storage: times the segment was
+        streamed) are each optional (None: not written).  The table's entries are not checked
+        here: they must be within 0..2^32 (krr_amd.api.FleetBatch.weighted_percentile checks)."""
+        _check_tensor(age_weights, "int64")
+        _check_tensor(value, "float64", series.n_segments)
+        if wsum is not None:
+            _check_tensor(wsum, "int64", series.n_segments)
+        if passes is not None:
+            _check_tensor(passes, "int32", series.n_segments)
+        _check_tensor(count, "int64", series.n_segments)
+        _check_tensor(flags, "int32", series.n_segments)
+        self._check(self._lib.krr_segmented_wquantile(
+            self._h, ctypes.byref(series), age_weights.data_ptr(), age_weights.numel(), int(p_num), int(p_den),
+            value.data_ptr(), *(None if t is None else t.data_ptr() for t in (wsum, passes)),
             count.data_ptr(), flags.data_ptr(), self._stream(stream)))
 
     def segmented_rollup(self, series: KrrSeries, window: int, align: int, win_offsets, wmin, wmax, wsum, wcount,

@@ -2,7 +2,7 @@
 reference's names) and ``FleetBatch``, the fleet statistics a custom strategy's ``run_batch``
 computes on the device (krr_amd.api.batch)."""
 from krr_amd.api.batch import (FleetBatch, FleetExceedance, FleetMoments, FleetOverlay, FleetProfile, FleetRollup,
-                               FleetStats, allocation_thresholds)
+                               FleetStats, allocation_thresholds, decay_weights, window_weights)
 
 __all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetOverlay", "FleetProfile", "FleetRollup",
-           "FleetStats", "allocation_thresholds"]
+           "FleetStats", "allocation_thresholds", "decay_weights", "window_weights"]

@@ -14,6 +14,7 @@ on the device, one launch per statistic instead of a Python loop per object:
     vs = batch.percentiles(ResourceType.CPU, ["50", "95", "99"], mode="linear")  # float64 [P, S]
     pods = batch.per_pod(ResourceType.CPU)         # a FleetBatch over one segment per pod + .pod_groups
     ov = batch.overlay(ResourceType.CPU)           # FleetOverlay: an object's pods folded slot by slot
+    w = batch.weighted_percentile(ResourceType.CPU, "95", decay_weights(1440, 10080))  # recency-weighted, exact
     batch.to_decimal(values, flags)                # list[Decimal]
 
 ``stats`` is one krr_segmented_stats pass (min and max are the first minimal / maximal sample's own
@@ -38,13 +39,14 @@ from typing import Mapping, Optional, Sequence
 import numpy as np
 
 from krr_amd import _native
-from krr_amd.core.engine import MODE_CODES, SimpleEngine, default_engine, percentile_params
+from krr_amd.core.engine import (MODE_CODES, WEIGHT_MAX, SimpleEngine, default_engine, percentile_fraction,
+                                 percentile_params, weight_table)
 from krr_amd.core.models.allocations import ResourceType
 from krr_amd.core.packing import PackedFleet, PackedSeries, pack_resource, pod_view
 from krr_amd.utils.prom_decimal import prom_decimal
 
 __all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetOverlay", "FleetProfile", "FleetRollup",
-           "FleetStats", "allocation_thresholds"]
+           "FleetStats", "allocation_thresholds", "decay_weights", "window_weights"]
 
 
 @dataclass
@@ -580,6 +582,52 @@ def allocation_thresholds(objects: Sequence, resource: ResourceType, which: str 
     return out
 
 
+def _check_table_args(length, **others) -> int:
+    for name, v in {"length": length, **others}.items():
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an int (slots), got {v!r}")
+    if length < 1:
+        raise ValueError(f"length must be at least 1, got {length!r}")
+    return int(length)
+
+
+def decay_weights(half_life: int, length: int) -> np.ndarray:
+    """uint64 [length]: the weight table of an exponential decay with ``half_life`` slots, for
+    ``FleetBatch.weighted_percentile``.  Entry a (the age: a slots before a series' last one) is
+    floor(2^32 * 2^(-a / half_life)), exactly: entry 0 is 2^32, entry k * half_life is 2^(32 - k),
+    the table never increases and is 0 from age 32 * half_life + 1 on.  ``length`` is normally the
+    longest series: an older slot takes the table's LAST entry.  With one sample a minute,
+    ``decay_weights(1440, 10080)`` is VPA's one-day half-life over a week."""
+    length = _check_table_args(length, half_life=half_life)
+    h = int(half_life)
+    if h < 1:
+        raise ValueError(f"half_life must be at least 1 slot, got {half_life!r}")
+    # floor(2^(e / h)) with e = 32 h - a = q h + r is floor(G[r] / 2^(32 - q)), G[r] = floor(2^32 * 2^(r / h)).
+    # 2^(r / h) is irrational for 0 < r < h, so a float64 estimate (within 2^-18 of 2^32 * 2^(r/h)) gives the
+    # floor except next to an integer, where the integers decide: g^h <= 2^(32 h + r) < (g + 1)^h.
+    est = np.ldexp(np.exp2(np.arange(h, dtype=np.float64) / h), 32)
+    g = np.floor(est).astype(np.uint64)
+    for r in np.flatnonzero(np.abs(est - np.rint(est)) < 1e-3)[1:]:  # r = 0 is 2^32 exactly
+        c = int(np.rint(est[r]))
+        g[r] = c if c**h <= 1 << (32 * h + int(r)) else c - 1
+    e = 32 * h - np.arange(length, dtype=np.int64)
+    live = e >= 0
+    q, r = np.divmod(np.where(live, e, 0), h)
+    return np.where(live, g[r] >> (32 - q).astype(np.uint64), np.uint64(0)).astype(np.uint64)
+
+
+def window_weights(last: int, length: int) -> np.ndarray:
+    """uint64 [length]: weight 1 for the newest ``last`` slots (ages 0 .. last - 1) and 0 before
+    them: "the percentile of the last day" without re-packing.  An older slot takes the table's
+    LAST entry, so ``length`` must exceed ``last`` for it to be 0."""
+    length = _check_table_args(length, last=last)
+    if not 0 <= last < length:
+        raise ValueError(f"last must lie in 0 .. length - 1 = {length - 1}, got {last!r}")
+    w = np.zeros(length, dtype=np.uint64)
+    w[:int(last)] = 1
+    return w
+
+
 def _slots(ps: PackedSeries) -> np.ndarray:
     """int64 [S]: each series' length in slots, from the offsets wherever they live."""
     offs = ps.offsets
@@ -763,6 +811,51 @@ class FleetBatch:
                                                  r["flags"], r["active"], r["sum"], r["max"], r["min"],
                                                  self.device, self.engine)
         return ov
+
+    def _wquantile(self, resource: ResourceType, percentile, weights) -> dict:
+        """``SimpleEngine.wquantile_series`` of the resource, cached per (resource, percentile as
+        a fraction, weight bytes)."""
+        resource = ResourceType(resource)
+        tab = weight_table(weights)
+        frac = percentile_fraction(percentile)
+        key = (resource, "wquantile", frac, tab.tobytes())
+        r = self._cache.get(key)
+        if r is None:
+            r = self._cache[key] = self.engine.wquantile_series(self.series(resource), tab, percentile)
+        return r
+
+    def weighted_percentile(self, resource: ResourceType, percentile, weights, return_flags: bool = False):
+        """float64 [S]: the exact WEIGHTED percentile of every object's series, a sample's weight
+        given by its age (krr_segmented_wquantile).  ``weights`` is a uint64 table indexed by age:
+        entry 0 weighs a series' last slot ("now"), entry a the slot a places before it, and the
+        table's last entry everything older (``decay_weights``, ``window_weights``, or any
+        integers within 0 .. 2^32).  With W the summed weight of an object's present samples and
+        C(v) that of its samples <= v, the answer is the smallest sample v with C(v) >= W * p / 100,
+        compared exactly: the weighted "inverted CDF" quantile, with unit weights
+        sorted(x)[ceil(n p / 100) - 1] — NOT the index rule of ``percentile(mode="sorted_lower")``.
+        ``percentile`` is anything ``Decimal(str(.))`` takes in (0, 100]; it becomes an exact
+        fraction, whose denominator may not exceed 10^15.  ValueError for a table that is empty,
+        not 1-D, of a float dtype, negative or above 2^32.  NaN where an object has no weight at
+        all (no sample, or only zero-weight ones) and where a flag says so (KRR_FLAG_EMPTY,
+        KRR_FLAG_NAN); ``return_flags``: also the uint32 [S] flags, for ``to_decimal``.  Cached
+        per (resource, percentile, weight bytes).  Works on a ``per_pod()`` view unchanged
+        (weights per pod).  On series packed without gaps (HistoryData lists) age counts SAMPLES,
+        not minutes: a series that ended early is not shifted, as for ``overlay(align="end")``."""
+        r = self._wquantile(resource, percentile, weights)
+        value = np.where((r["wsum"] == 0) | (r["flags"] != 0), np.nan, r["value"])
+        return (value, r["flags"]) if return_flags else value
+
+    def weight_sums(self, resource: ResourceType, weights) -> np.ndarray:
+        """float64 [S]: every object's total weight / 2^32 under ``weights``: with
+        ``decay_weights`` the effective sample count behind ``weighted_percentile``.  Taken from
+        a cached ``weighted_percentile`` of the same table when there is one (the total does not
+        depend on the percentile), else one launch at p = 100."""
+        resource = ResourceType(resource)
+        tab = weight_table(weights).tobytes()
+        hit = next((v for k, v in self._cache.items()
+                    if len(k) == 4 and k[:2] == (resource, "wquantile") and k[3] == tab), None)
+        r = hit if hit is not None else self._wquantile(resource, 100, weights)
+        return r["wsum"].astype(np.float64) / float(WEIGHT_MAX)
 
     def percentiles(self, resource: ResourceType, percentiles: Sequence, mode: str = "ref_index",
                     return_flags: bool = False):

@@ -42,6 +42,45 @@ def percentile_params(percentile, mode: str) -> _native.KrrPercentileParams:
     return params
 
 
+WEIGHT_MAX = 1 << 32  # the largest age weight: a segment's total stays below 2^63
+P_DEN_MAX = 10**15    # krr_percentile_params' bound on p_den
+
+
+def percentile_fraction(percentile) -> tuple:
+    """``percentile`` (anything ``Decimal(str(.))`` takes, 0 < p <= 100) as the exact fraction
+    (p_num, p_den) in lowest terms that krr_segmented_wquantile compares with.  ValueError
+    outside (0, 100] or when the denominator exceeds 10^15."""
+    from decimal import Decimal, InvalidOperation
+    from fractions import Fraction
+
+    try:
+        d = Decimal(str(percentile))
+    except InvalidOperation:
+        raise ValueError(f"percentile {percentile!r} is not a number") from None
+    if not d.is_finite() or not 0 < d <= 100:
+        raise ValueError(f"percentile must lie in (0, 100], got {percentile!r}")
+    f = Fraction(d)
+    if f.denominator > P_DEN_MAX:
+        raise ValueError(f"percentile {percentile!r} needs a denominator above 10^15")
+    return f.numerator, f.denominator
+
+
+def weight_table(weights) -> np.ndarray:
+    """``weights`` as the contiguous uint64 table krr_segmented_wquantile reads.  ValueError when
+    it is not a 1-D array of an unsigned (or non-negative signed) integer dtype, is empty, or
+    has an entry above 2^32."""
+    w = np.asarray(weights)
+    if w.ndim != 1 or w.size == 0:
+        raise ValueError(f"weights must be a non-empty 1-D array, got shape {w.shape}")
+    if w.dtype == bool or not np.issubdtype(w.dtype, np.integer):
+        raise ValueError(f"weights must have an integer dtype (uint64), got {w.dtype}")
+    if np.issubdtype(w.dtype, np.signedinteger) and (w < 0).any():
+        raise ValueError("weights must not be negative")
+    if (w > WEIGHT_MAX).any():
+        raise ValueError("weights must not exceed 2^32")
+    return np.ascontiguousarray(w, dtype=np.uint64)
+
+
 @dataclass
 class RawResults:
     """Per-object raw proposals as the kernels return them (host numpy arrays)."""
@@ -362,6 +401,27 @@ class SimpleEngine:
                                          "count": np.int64, "flags": np.int32},
                                  rows={**{k: R for k in ints}, "excess": R})
 
+    def wquantile_series(self, ps: PackedSeries, weights, percentile) -> dict:
+        """Per segment the exact weighted percentile under age-indexed integer weights
+        (krr_segmented_wquantile): host arrays ``value`` (float64), ``wsum`` (uint64: the total
+        weight of the present samples), ``passes`` (int32: times the segment was streamed),
+        ``count`` (int64) and ``flags`` (uint32), [S] each.  ``weights`` is a 1-D unsigned
+        integer table with entries within 0..2^32 (``weight_table`` says what else is refused),
+        ``percentile`` anything ``percentile_fraction`` takes.  The table is uploaded once per
+        call and serves every chunk; chunks and synchronisation as ``stats_series``."""
+        tab = weight_table(weights)
+        p_num, p_den = percentile_fraction(percentile)
+        ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        parts, d_tab = [], None
+        for part in self._series_parts(ps):
+            if d_tab is None:
+                d_tab = self._upload_table(tab)
+            parts.append(self._wquantile_part(ctx, part, d_tab, p_num, p_den))
+        host = self._host_concat(parts, {"value": np.float64, "wsum": np.int64, "passes": np.int32,
+                                         "count": np.int64, "flags": np.int32})
+        host["wsum"] = host["wsum"].view(np.uint64)
+        return host
+
     def rollup_series(self, ps: PackedSeries, window: int, align: int) -> dict:
         """Every segment of one series cut into windows of ``window`` slots
         (krr_segmented_rollup; ``align`` KRR_ROLLUP_START or KRR_ROLLUP_END): ``wcount`` (int32),
@@ -600,6 +660,26 @@ class SimpleEngine:
                                  ("excess", torch.float64, R), ("count", torch.int64, 0), ("flags", torch.int32, 0)), n)
             ctx.segmented_exceed(series, thr, R, out["above"], out["excess"], out["longest"], out["head"],
                                  out["tail"], out["last"], out["count"], out["flags"])
+        return out
+
+    def _upload_table(self, tab: np.ndarray):
+        """A uint64 weight table in HBM, as the int64 storage the binding takes."""
+        import torch
+
+        return torch.from_numpy(tab.view(np.int64)).to(torch.device("cuda", self.device))
+
+    def _wquantile_part(self, ctx, part: PackedSeries, table, p_num: int, p_den: int) -> dict:
+        """Upload (host series) and one krr_segmented_wquantile launch on the current stream with
+        the weight table ``table`` (int64 storage, already on the device): the chunk's device
+        tensors."""
+        import torch
+
+        with torch.cuda.device(self.device):
+            series = self._part_series(ctx, part)
+            out = self._outputs((("value", torch.float64, 0), ("wsum", torch.int64, 0), ("passes", torch.int32, 0),
+                                 ("count", torch.int64, 0), ("flags", torch.int32, 0)), part.n_segments)
+            ctx.segmented_wquantile(series, table, p_num, p_den, out["value"], out["wsum"], out["passes"],
+                                    out["count"], out["flags"])
         return out
 
     def _resident(self, part: PackedSeries) -> PackedSeries:

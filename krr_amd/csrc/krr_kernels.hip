@@ -4139,6 +4139,323 @@ __global__ __launch_bounds__(64) void k_overlay(OverlayArgs A) {
     }
 }
 
+// ------------------------------ WQUANTILE ----------------------------------
+// krr_segmented_wquantile: per segment the exact weighted percentile under an age-indexed integer
+// weight table (krr_amd.h states the rule).  The select kernels keep rank counts ("the top T
+// keys"); here the number of keys the answer needs is unknown until the total weight W is, so the
+// segment is streamed several times, hselect's way:
+//   pass 0     W, the NaN count, how many present samples carry weight, and the least and greatest
+//              key among those: the first key range [lo, hi].  lo == hi (an all-equal series, or a
+//              table that leaves one sample) is the answer already;
+//   histogram  bin = (key - lo) >> sh over [lo, hi]: a 64-bit weight and a 32-bit count per bin
+//              (LDS atomics on integers), the weight of the keys below lo summed per lane.  The first
+//              bin whose cumulative weight C satisfies C * den >= W * num (128-bit products) holds
+//              the answer: a bin of one key is the answer, one of at most kWqCap samples is
+//              collected, any other becomes the next [lo, hi], clipped to the least and greatest key
+//              the pass met in range (so many copies of ONE key end the search a pass later);
+//   collect    the (key, weight) pairs of [lo, hi] into LDS, where the same histogram step runs
+//              over the buffer instead of the stream until one key is left.
+// A zero-weight sample takes no part after pass 0.  Every pass finds a slot's age from a SegCursor
+// and reads its weight from the table (L2-resident: 80 KB for 10,080 slots); a lane's two slots
+// have adjacent ages.  All sums are integers: the result does not depend on the order of the
+// atomics, the parity of the start offset or the launch.
+// TERMINATION.  With bits = the width of hi - lo, a histogram step leaves a range of at most
+// bits - kWqBits bits, and at bits <= kWqBits every bin is one key.  So at most kWqMaxHist =
+// ceil(64 / kWqBits) histogram passes, and passes <= 1 + kWqMaxHist + 1 = kWqMaxPasses.
+// LDS: kWqBins x (8 + 4) B + kWqCap x 16 B = 20 KiB per wave: 8 waves per CU, 2 per SIMD.
+constexpr int kWqBits = 10;
+constexpr uint32_t kWqBins = 1u << kWqBits;
+constexpr uint32_t kWqCap = 512;
+constexpr int kWqMaxHist = (64 + kWqBits - 1) / kWqBits;  // 7
+constexpr int kWqMaxPasses = 1 + kWqMaxHist + 1;          // 9
+static_assert(kWqBins % kWave == 0, "bins per lane");
+static_assert(kWqMaxPasses == 9, "krr_amd.h states the bound on out_passes");
+
+// the table the launch weighs with, and the weights of this lane's c[u] of the chunk in hand
+struct WqTable {
+    const uint64_t* tab;
+    int64_t nw, L;
+    __device__ __forceinline__ void weights(const SegCursor& at, int u, uint64_t& wx, uint64_t& wy) const {
+        int64_t ix = at.row_base(u) + 2 * at.lane, iy = ix + 1;
+        if (at.edge(u)) {  // slot 0 and slot L - 1 (krr_geom.h)
+            ix = 0;
+            iy = L - 1;
+        }
+        // padding units lie past the segment (a negative age): any entry does, their value is NaN
+        wx = tab[clamp_i64(L - 1 - ix, 0, nw - 1)];
+        wy = tab[clamp_i64(L - 1 - iy, 0, nw - 1)];
+    }
+};
+
+struct WqTotalsProc {
+    WqTable T;
+    SegCursor at;
+    uint64_t w_l, kmn, kmx;  // per lane: weight, least and greatest key of positive weight
+    uint32_t nan_l, pos_l;   // per lane: NaN slots (padding included), samples of positive weight
+    __device__ __forceinline__ WqTotalsProc(const WqTable& t, int64_t beg, int64_t end, int lane)
+        : T(t), at(seg_geom(beg, end), lane), w_l(0), kmn(~0ull), kmx(0), nan_l(0), pos_l(0) {}
+    __device__ __forceinline__ void slot(double d, uint64_t w) {
+        const uint64_t x = dbits(d), key = okey(x);
+        const bool nan = is_nan_bits(x);
+        w = nan ? 0ull : w;
+        nan_l += nan ? 1u : 0u;
+        w_l += w;
+        if (w) {
+            kmn = key < kmn ? key : kmn;
+            kmx = key > kmx ? key : kmx;
+            ++pos_l;
+        }
+    }
+    __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            uint64_t wx, wy;
+            T.weights(at, u, wx, wy);
+            slot(c[u].x, wx);
+            slot(c[u].y, wy);
+        }
+        at.next();
+    }
+};
+
+struct WqHistProc {
+    WqTable T;
+    SegCursor at;
+    unsigned long long* wbin;
+    uint32_t* cbin;
+    uint64_t lo, span;
+    uint32_t sh;
+    uint64_t below_l;   // per lane: weight of the keys below lo
+    uint64_t kmn, kmx;  // per lane: least and greatest key met inside [lo, hi]
+    __device__ __forceinline__ WqHistProc(const WqTable& t, int64_t beg, int64_t end, int lane)
+        : T(t), at(seg_geom(beg, end), lane), below_l(0), kmn(~0ull), kmx(0) {}
+    __device__ __forceinline__ void slot(double d, uint64_t w) {
+        const uint64_t x = dbits(d), key = okey(x);
+        if (is_nan_bits(x) || w == 0) return;
+        const uint64_t t = key - lo;
+        if (key < lo) {
+            below_l += w;
+        } else if (t <= span) {
+            const uint32_t b = (uint32_t)(t >> sh);  // < kWqBins: span >> sh < kWqBins
+            atomicAdd(&wbin[b], (unsigned long long)w);
+            atomicAdd(&cbin[b], 1u);
+            kmn = key < kmn ? key : kmn;
+            kmx = key > kmx ? key : kmx;
+        }
+    }
+    __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            uint64_t wx, wy;
+            T.weights(at, u, wx, wy);
+            slot(c[u].x, wx);
+            slot(c[u].y, wy);
+        }
+        at.next();
+    }
+};
+
+struct WqCollectProc {
+    WqTable T;
+    SegCursor at;
+    uint64_t* pairs;  // key at [2 i], weight at [2 i + 1]
+    uint64_t lo, span;
+    uint32_t cnt;  // wave-uniform: pairs met (only the first kWqCap are stored)
+    __device__ __forceinline__ WqCollectProc(const WqTable& t, int64_t beg, int64_t end, int lane)
+        : T(t), at(seg_geom(beg, end), lane), cnt(0) {}
+    __device__ __forceinline__ void slot(double d, uint64_t w) {
+        const uint64_t x = dbits(d), key = okey(x);
+        const bool in = !is_nan_bits(x) && w != 0 && key - lo <= span;
+        const uint64_t m = ballot(in);
+        if (m) {
+            const uint32_t i = cnt + lane_prefix(m);
+            if (in && i < kWqCap) {
+                pairs[2 * i] = key;
+                pairs[2 * i + 1] = w;
+            }
+            cnt = uni32(cnt + popc64(m));
+        }
+    }
+    __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            uint64_t wx, wy;
+            T.weights(at, u, wx, wy);
+            slot(c[u].x, wx);
+            slot(c[u].y, wy);
+        }
+        at.next();
+    }
+};
+
+// the rule's compare: cumulative weight c reaches p percent of W (target = W * p_num, den = 100 * p_den)
+__device__ __forceinline__ bool wq_reached(uint64_t c, uint64_t den, unsigned __int128 target) {
+    return (unsigned __int128)c * den >= target;
+}
+
+// The first bin whose cumulative weight, `below` included, reaches the target: its index, the
+// weight before it and its count.  Lane l's share is bins [16 l, 16 l + 16).  False when no bin
+// does (never, while [lo, hi] holds every key of positive weight not counted in `below`).
+__device__ __forceinline__ bool wq_find(const unsigned long long* wbin, const uint32_t* cbin, uint64_t below,
+                                        uint64_t den, unsigned __int128 target, int lane, uint32_t& b,
+                                        uint64_t& before, uint32_t& cnt) {
+    constexpr uint32_t per = kWqBins / kWave;
+    uint64_t t = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < per; ++j) t += wbin[(uint32_t)lane * per + j];
+    const uint64_t incl = wave_scan64(t, 0ull, OpAdd64{});
+    const uint64_t m = ballot(wq_reached(below + incl, den, target));
+    if (!m) return false;
+    const int src = __ffsll((long long)m) - 1;
+    const uint64_t base = below + lane_bcast64(incl - t, src);
+    // second level: lane j < per looks at bin src * per + j
+    const uint64_t h = (uint32_t)lane < per ? wbin[(uint32_t)src * per + (uint32_t)lane] : 0ull;
+    const uint64_t incl2 = wave_scan64(h, 0ull, OpAdd64{});
+    const uint64_t m2 = ballot((uint32_t)lane < per && wq_reached(base + incl2, den, target));
+    if (!m2) return false;
+    const int sel = __ffsll((long long)m2) - 1;
+    b = (uint32_t)src * per + (uint32_t)sel;
+    before = base + lane_bcast64(incl2 - h, sel);
+    cnt = uni32(cbin[b]);
+    return true;
+}
+
+struct WqArgs {
+    SeriesArgs h;
+    const uint64_t* tab;
+    int64_t nw;
+    uint64_t p_num, den;  // den = 100 * p_den
+    double* out_v;
+    uint64_t* out_w;   // may be null
+    uint32_t* out_p;   // may be null
+};
+
+__global__ __launch_bounds__(64) void k_wquantile(WqArgs A) {
+    __shared__ unsigned long long wbin[kWqBins];
+    __shared__ uint32_t cbin[kWqBins];
+    __shared__ uint64_t pairs[2 * kWqCap];
+    const int lane = threadIdx.x;
+    for (int64_t bi = blockIdx.x; bi < A.h.S; bi += gridDim.x) {
+        const SeriesItem item = series_item(A.h, bi);
+        const int64_t s = item.s, beg = item.beg, end = item.end;  // named: the lambdas below capture them
+        const uint64_t L = (uint64_t)(end - beg);
+        const WqTable T{A.tab, A.nw, (int64_t)L};
+        // every stream_segment call gets bounds the compiler cannot tell from the other calls', or it
+        // would hoist the stream's address set-up and keep it live throughout (select_segment)
+        auto opaque = [&](int64_t& b, int64_t& e) {
+            b = beg;
+            e = end;
+            asm volatile("" : "+s"(b), "+s"(e));
+        };
+        int64_t ob, oe;
+
+        // ---- pass 0: totals
+        WqTotalsProc P0(T, beg, end, lane);
+        opaque(ob, oe);
+        const uint32_t pad = stream_segment<true>(A.h.vals, ob, oe, P0, lane);
+        const uint64_t nnan = wave_sum_u32(P0.nan_l) - pad;
+        const SeriesCount sc = series_count(A.h, L, L - nnan);
+        const uint64_t W = wave_sum_u64(P0.w_l);
+        uint64_t lo = wave_min_u64(P0.kmn), hi = wave_max_u64(P0.kmx);
+        uint32_t cnt = wave_sum_u32(P0.pos_l);
+        uint32_t passes = 1;
+        bool ok = !sc.flags && W != 0;
+
+        if (ok && lo != hi) {
+            const unsigned __int128 target = (unsigned __int128)W * A.p_num;
+            uint64_t below = 0;
+            auto zero_bins = [&]() {
+                for (uint32_t i = lane; i < kWqBins; i += kWave) {
+                    wbin[i] = 0;
+                    cbin[i] = 0;
+                }
+                __syncthreads();
+            };
+            // the bin the histogram over [lo, hi] points at becomes [lo, hi]
+            auto narrow = [&](uint32_t sh) {
+                uint32_t b;
+                uint64_t before;
+                __syncthreads();
+                if (!wq_find(wbin, cbin, below, A.den, target, lane, b, before, cnt)) return false;
+                __syncthreads();
+                const uint64_t nlo = lo + ((uint64_t)b << sh), w = (1ull << sh) - 1;
+                hi = hi - nlo <= w ? hi : nlo + w;
+                lo = nlo;
+                below = before;
+                return true;
+            };
+            auto shift_of = [&]() {
+                const uint64_t span = hi - lo;
+                const int bits = span ? 64 - __clzll((long long)span) : 0;
+                return bits > kWqBits ? (uint32_t)(bits - kWqBits) : 0u;
+            };
+#pragma unroll 1
+            for (int hp = 0; ok && lo != hi; ++hp) {
+                if (cnt <= kWqCap) {
+                    // ---- collect pass, then the histogram step over the buffer until one key is left
+                    WqCollectProc CP(T, beg, end, lane);
+                    CP.pairs = pairs;
+                    CP.lo = lo;
+                    CP.span = hi - lo;
+                    opaque(ob, oe);
+                    stream_segment<true>(A.h.vals, ob, oe, CP, lane);
+                    ++passes;
+                    __syncthreads();
+                    ok = CP.cnt == cnt;
+#pragma unroll 1
+                    for (int it = 0; ok && lo != hi; ++it) {
+                        if (it >= kWqMaxHist) {
+                            ok = false;
+                            break;
+                        }
+                        const uint32_t sh = shift_of();
+                        const uint64_t span = hi - lo;
+                        zero_bins();
+                        for (uint32_t i = lane; i < CP.cnt; i += kWave) {
+                            const uint64_t t = pairs[2 * i] - lo;
+                            if (t <= span) {
+                                atomicAdd(&wbin[(uint32_t)(t >> sh)], (unsigned long long)pairs[2 * i + 1]);
+                                atomicAdd(&cbin[(uint32_t)(t >> sh)], 1u);
+                            }
+                        }
+                        ok = narrow(sh);
+                    }
+                    break;
+                }
+                if (hp >= kWqMaxHist) {
+                    ok = false;
+                    break;
+                }
+                // ---- histogram pass over [lo, hi]
+                WqHistProc HP(T, beg, end, lane);
+                HP.wbin = wbin;
+                HP.cbin = cbin;
+                HP.lo = lo;
+                HP.span = hi - lo;
+                HP.sh = shift_of();
+                zero_bins();
+                opaque(ob, oe);
+                stream_segment<true>(A.h.vals, ob, oe, HP, lane);
+                ++passes;
+                below = wave_sum_u64(HP.below_l);
+                ok = narrow(HP.sh);
+                // the keys met in the old range bound the new one too: a bin of many copies of one key
+                // (a mostly-zero series) is known for that on the next pass, not after kWqMaxHist of them
+                const uint64_t mn = wave_min_u64(HP.kmn), mx = wave_max_u64(HP.kmx);
+                lo = lo < mn ? mn : lo;
+                hi = hi > mx ? mx : hi;
+            }
+        }
+        if (lane == 0) {
+            A.out_v[s] = bitsd(ok ? okey_inv(lo) : kQuietNaN);
+            if (A.out_w) A.out_w[s] = sc.flags & KRR_FLAG_NAN ? 0ull : W;
+            if (A.out_p) A.out_p[s] = passes;
+            sc.write(A.h, s);
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace krr
 #include "krr_kll.h"
 namespace krr {
@@ -4923,6 +5240,22 @@ int krr_segmented_exceed(krr_ctx* ctx, const krr_series* series, const double* t
             case 3: hipLaunchKernelGGL(k_exceed<3>, grid, block, 0, st, A); break;
             default: hipLaunchKernelGGL(k_exceed<4>, grid, block, 0, st, A); break;
         }
+        return KRR_OK;
+    });
+}
+
+int krr_segmented_wquantile(krr_ctx* ctx, const krr_series* series, const uint64_t* age_weights, int64_t n_weights,
+                            int64_t p_num, int64_t p_den, double* out_value, uint64_t* out_wsum,
+                            uint32_t* out_passes, int64_t* out_count, uint32_t* out_flags, void* stream) {
+    return series_entry(ctx, series, out_count, out_flags, KRR_OK, [&](const SeriesArgs& H, dim3 grid) -> int {
+        if (!age_weights || n_weights < 1)
+            return set_err(ctx, KRR_E_INVALID, "null age_weights or n_weights < 1%s: %lld", "", (long long)n_weights);
+        if (p_num <= 0 || p_den <= 0 || p_den > 1000000000000000ll || p_num > 100 * p_den)
+            return set_err(ctx, KRR_E_INVALID, "percentile outside (0, 100] or p_den > 10^15%s", "");
+        if (!out_value || !out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+        const WqArgs A{H, age_weights, n_weights, (uint64_t)p_num, 100ull * (uint64_t)p_den, out_value, out_wsum,
+                       out_passes};
+        hipLaunchKernelGGL(k_wquantile, grid, dim3(64), 0, (hipStream_t)stream, A);
         return KRR_OK;
     });
 }
