@@ -621,6 +621,82 @@ int krr_sketch_query(krr_ctx* ctx, int64_t n_segments, const uint32_t* counts, c
                      const double* vmax, const krr_sketch_params* sp, const krr_percentile_params* params,
                      double* out_value, int64_t* out_count, uint32_t* out_flags, void* stream);
 
+/* Per segment a HISTOGRAM OF WEIGHTS over data-independent log-linear bins, from one pass over the
+ * values: what krr_segmented_wquantile cannot give: several percentiles from one pass, rows that
+ * merge across time slices and ranks, at the price of a value error of one bin
+ * (krr_amd.api.FleetBatch.histogram; Kubernetes VPA's decaying histogram).  series, age_weights,
+ * age_base and the outputs are device pointers; bins is a host struct.
+ * Bins.  `bins` is a krr_sketch_params and the row layout is krr_sketch_build's, width =
+ * krr_sketch_width(bins) words of uint64 per segment, nbins = octaves << mantissa_bits:
+ *   [0] negative   [1] +-0   [2] (0, 2^e_lo)   [3 .. 3 + nbins) log-linear   [3 + nbins] the rest,
+ * +Inf included.  A sample's bin is taken from its bits (derived, not looked up: no table of
+ * edges); it never decreases as the sample's key (okey) increases.
+ * Age and weight.  Slot i of a segment of L slots has age
+ *   a = age_base[s] + (L - 1 - i)
+ * and weight age_weights[min(a, n_weights - 1)]; age_base NULL is all 0, and then ages and weights
+ * are krr_segmented_wquantile's.  age_base is what makes time slices mergeable: the OLDER slice of
+ * a series is built with age_base = the number of slots that follow it, and the two rows then add
+ * up, word for word, to the row of the whole.  The array lives on the device and is not read by
+ * the host, so a negative entry is not an error: it is taken as 0.  An age past the table's end
+ * takes the last entry, with or without age_base.  Weights <= 2^32 and fewer than 2^31 slots
+ * (age_base included in neither) keep a row's sum below 2^63; the kernel does NOT validate the
+ * table, a larger entry makes the sums wrap, nothing else.
+ * Outputs, with P = the present slots (every slot, or the non-NaN slots when gaps_are_nan):
+ *   - out_hist[s][b] = the summed weight of the samples of P whose bin is b;
+ *   - out_wsum[s] = W, the row's sum (derived from the same samples, not from the row);
+ *   - out_wmin[s], out_wmax[s] = the least and the greatest sample of P of POSITIVE weight under
+ *     okey, with its own bits (-0.0 below +0.0, +-Inf ordinary values); the quiet NaN
+ *     0x7FF8000000000000 when W == 0;
+ *   - out_count, out_flags: bit-identical to krr_segmented_stats on the same series;
+ *   - KRR_FLAG_NAN (a NaN sample in the compact layout): a row of zeros, W = 0, wmin = wmax = the
+ *     quiet NaN;
+ *   - an empty segment, or one without weight: a row of zeros, W = 0, the quiet NaNs;
+ *   - out_wsum, out_wmin and out_wmax may each be NULL and are then not written; out_hist,
+ *     out_count and out_flags are required.
+ * Determinism.  Every accumulation is an integer sum: the same samples, table and age_base give
+ * the same bits at ANY start offset, whole or cut into slices and added, on any launch and under
+ * any order of the LDS atomics, as for krr_segmented_wquantile.
+ * KRR_E_INVALID, while n_segments > 0: a null ctx or series; invalid bins (krr_sketch_width < 0);
+ * age_weights NULL; n_weights < 1; out_hist, out_count or out_flags NULL.  KRR_E_UNSUPPORTED:
+ * width > 4096 (the row is accumulated in width x 8 B of LDS, 32 KiB at most).  n_segments == 0
+ * launches nothing.  Asynchronous, no synchronisation.  One wave per segment. */
+int krr_segmented_whist(krr_ctx* ctx, const krr_series* series, const krr_sketch_params* bins,
+                        const uint64_t* age_weights, int64_t n_weights, const int64_t* age_base,
+                        uint64_t* out_hist, uint64_t* out_wsum, double* out_wmin, double* out_wmax,
+                        int64_t* out_count, uint32_t* out_flags, void* stream);
+
+/* Percentiles read from histogram rows (krr_segmented_whist's, or sums of them) without touching
+ * the samples again.  hist [n_rows][width], wmin / wmax [n_rows] and the outputs are device
+ * pointers; p_num / p_den are HOST arrays of n_percentiles entries, 1 .. KRR_MAX_PERCENTILES, each
+ * 0 < p_num / p_den <= 100 with p_den <= 10^15.  The outputs are row-major [n_percentiles][n_rows].
+ * The answer bin.  With W the row's sum and C(b) the summed weight of bins 0 .. b, out_bin is the
+ * first b with
+ *   C(b) * (100 * p_den) >= W * p_num,
+ * compared in exact 128-bit integers: krr_segmented_wquantile's rule on bins.  Because a sample's
+ * bin never decreases with its key, this is the bin that holds krr_segmented_wquantile's exact
+ * answer for the same samples, table and percentile (derived, and held to it by the tests).
+ * The bracket.  Log-linear bin 3 + i covers [2^E (1 + j 2^-m), 2^E (1 + (j + 1) 2^-m)) with
+ * E = e_lo + (i >> m), j = i & (2^m - 1); the edges are built from powers of two and are exact.
+ *   - out_lower = max(lower edge, wmin), out_upper = min(upper edge, wmax), by okey order.
+ *     out_upper is the "end of the bucket", clamped: never below the exact weighted percentile,
+ *     at most (1 + 2^-m) times it in a log-linear bin, and p = 100 gives wmax itself;
+ *   - bin 1 (+-0): lower = upper = +0.0, no flag, whichever zeros the row holds (so p = 100 of a
+ *     row whose wmax is -0.0 gives +0.0: wmax as a number, not its bits);
+ *   - bin 0: [wmin, min(-0.0, wmax)]; bin 2: [max(+0.0, wmin), min(2^e_lo, wmax)]; the top bin:
+ *     [max(2^(e_lo + octaves), wmin), wmax].  These three carry KRR_FLAG_SKETCH_RANGE: the bracket
+ *     is as wide as the data, not as a bin;
+ *   - W == 0: out_bin = -1, both doubles the quiet NaN 0x7FF8000000000000, KRR_FLAG_EMPTY.
+ * wmin / wmax of a merged row are the okey-least / greatest of the parts', NaN ignored (the caller
+ * merges them).  A percentile gives the same bits alone as inside a launch of several.
+ * KRR_E_INVALID: a null ctx; invalid bins; n_rows < 0; n_percentiles outside
+ * 1 .. KRR_MAX_PERCENTILES; p_num or p_den NULL; a percentile outside (0, 100] or p_den > 10^15;
+ * while n_rows > 0, any other pointer NULL.  KRR_E_UNSUPPORTED: width > 4096.  n_rows == 0
+ * launches nothing.  Asynchronous, no synchronisation.  One wave per row. */
+int krr_whist_query(krr_ctx* ctx, int64_t n_rows, const krr_sketch_params* bins, const uint64_t* hist,
+                    const double* wmin, const double* wmax, const int64_t* p_num, const int64_t* p_den,
+                    int32_t n_percentiles, int32_t* out_bin, double* out_lower, double* out_upper,
+                    uint32_t* out_flags, void* stream);
+
 /* ---- KLL sketch (row format 2): a RANK-error bound whatever the data, an exact top tail,
  * and a bounded fold ----
  * (north_star: "an optional mergeable t-digest/KLL sketch mode"; the log-linear sketch above

@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = (
     "krr_segmented_moments",
     "krr_segmented_exceed",
     "krr_segmented_wquantile",
+    "krr_segmented_whist",
+    "krr_whist_query",
     "krr_segmented_rollup",
     "krr_pods_overlay",
     "krr_simple_run",
@@ -310,6 +312,13 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_segmented_exceed.restype = ctypes.c_int
         lib.krr_segmented_wquantile.argtypes = [vp, sp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
         lib.krr_segmented_wquantile.restype = ctypes.c_int
+        lib.krr_segmented_whist.argtypes = [vp, sp, ctypes.POINTER(KrrSketchParams), vp, i64, vp, vp, vp, vp, vp, vp,
+                                            vp, vp]
+        lib.krr_segmented_whist.restype = ctypes.c_int
+        lib.krr_whist_query.argtypes = [vp, i64, ctypes.POINTER(KrrSketchParams), vp, vp, vp,
+                                        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.c_int32, vp, vp, vp, vp, vp]
+        lib.krr_whist_query.restype = ctypes.c_int
         lib.krr_segmented_rollup.argtypes = [vp, sp, i64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_segmented_rollup.restype = ctypes.c_int
         lib.krr_pods_overlay.argtypes = [vp, sp, vp, i64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -584,6 +593,49 @@ class Context:
             self._h, ctypes.byref(series), age_weights.data_ptr(), age_weights.numel(), int(p_num), int(p_den),
             value.data_ptr(), *(None if t is None else t.data_ptr() for t in (wsum, passes)),
             count.data_ptr(), flags.data_ptr(), self._stream(stream)))
+
+    def segmented_whist(self, series: KrrSeries, bins: KrrSketchParams, age_weights, age_base, hist, wsum, wmin,
+                        wmax, count, flags, stream=None) -> None:
+        """Per segment a histogram of integer weights over the log-linear bins ``bins``, from one
+        pass (krr_segmented_whist).  ``age_weights`` as ``segmented_wquantile`` takes it (int64
+        storage read as uint64, not checked here); ``age_base`` int64 [S] or None (all 0): slot i
+        of L has age age_base[s] + L - 1 - i.  ``hist`` int64 [S, width] (uint64 words, below
+        2^63 for a valid table), ``count`` int64 [S] and ``flags`` int32 [S] are required;
+        ``wsum`` (int64 storage), ``wmin`` and ``wmax`` (float64) [S] are each optional (None:
+        not written)."""
+        S = series.n_segments
+        _check_tensor(age_weights, "int64")
+        if age_base is not None:
+            _check_tensor(age_base, "int64", S)
+        _check_tensor(hist, "int64", S * self.sketch_width(bins))
+        for t, dt in ((wsum, "int64"), (wmin, "float64"), (wmax, "float64")):
+            if t is not None:
+                _check_tensor(t, dt, S)
+        _check_tensor(count, "int64", S)
+        _check_tensor(flags, "int32", S)
+        self._check(self._lib.krr_segmented_whist(
+            self._h, ctypes.byref(series), ctypes.byref(bins), age_weights.data_ptr(), age_weights.numel(),
+            None if age_base is None else age_base.data_ptr(), hist.data_ptr(),
+            *(None if t is None else t.data_ptr() for t in (wsum, wmin, wmax)),
+            count.data_ptr(), flags.data_ptr(), self._stream(stream)))
+
+    def whist_query(self, hist, wmin, wmax, bins: KrrSketchParams, fractions, out_bin, out_lower, out_upper,
+                    out_flags, stream=None) -> None:
+        """Percentiles read from histogram rows (krr_whist_query).  ``hist`` int64 [R, width],
+        ``wmin`` / ``wmax`` float64 [R]; ``fractions`` 1 .. KRR_MAX_PERCENTILES pairs
+        (p_num, p_den); ``out_bin`` int32, ``out_lower`` / ``out_upper`` float64 and
+        ``out_flags`` int32, each [len(fractions), R]."""
+        R, P = wmin.numel(), len(fractions)
+        _check_tensor(hist, "int64", R * self.sketch_width(bins))
+        _check_tensor(wmax, "float64", R)
+        for t, dt in ((out_bin, "int32"), (out_lower, "float64"), (out_upper, "float64"), (out_flags, "int32")):
+            _check_tensor(t, dt, P * R)
+        nums = (ctypes.c_int64 * max(P, 1))(*(int(f[0]) for f in fractions))
+        dens = (ctypes.c_int64 * max(P, 1))(*(int(f[1]) for f in fractions))
+        self._check(self._lib.krr_whist_query(
+            self._h, R, ctypes.byref(bins), hist.data_ptr(), wmin.data_ptr(), wmax.data_ptr(), nums, dens, P,
+            out_bin.data_ptr(), out_lower.data_ptr(), out_upper.data_ptr(), out_flags.data_ptr(),
+            self._stream(stream)))
 
     def segmented_rollup(self, series: KrrSeries, window: int, align: int, win_offsets, wmin, wmax, wsum, wcount,
                          count, flags, stream=None) -> None:

@@ -1,8 +1,10 @@
 """Public plugin-author surface: ``krr_amd.api.strategies`` / ``krr_amd.api.models`` (the
 reference's names) and ``FleetBatch``, the fleet statistics a custom strategy's ``run_batch``
 computes on the device (krr_amd.api.batch)."""
-from krr_amd.api.batch import (FleetBatch, FleetExceedance, FleetMoments, FleetOverlay, FleetProfile, FleetRollup,
-                               FleetStats, allocation_thresholds, decay_weights, window_weights)
+from krr_amd.api.batch import (FleetBatch, FleetExceedance, FleetHistogram, FleetMoments, FleetOverlay, FleetProfile,
+                               FleetRollup, FleetStats, HistogramBins, allocation_thresholds, decay_weights,
+                               default_bins, window_weights)
 
-__all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetOverlay", "FleetProfile", "FleetRollup",
-           "FleetStats", "allocation_thresholds", "decay_weights", "window_weights"]
+__all__ = ["FleetBatch", "FleetExceedance", "FleetHistogram", "FleetMoments", "FleetOverlay", "FleetProfile",
+           "FleetRollup", "FleetStats", "HistogramBins", "allocation_thresholds", "decay_weights", "default_bins",
+           "window_weights"]

@@ -15,6 +15,7 @@ on the device, one launch per statistic instead of a Python loop per object:
     pods = batch.per_pod(ResourceType.CPU)         # a FleetBatch over one segment per pod + .pod_groups
     ov = batch.overlay(ResourceType.CPU)           # FleetOverlay: an object's pods folded slot by slot
     w = batch.weighted_percentile(ResourceType.CPU, "95", decay_weights(1440, 10080))  # recency-weighted, exact
+    h = batch.histogram(ResourceType.CPU, decay_weights(1440, 10080))  # FleetHistogram: mergeable, many percentiles
     batch.to_decimal(values, flags)                # list[Decimal]
 
 ``stats`` is one krr_segmented_stats pass (min and max are the first minimal / maximal sample's own
@@ -45,8 +46,9 @@ from krr_amd.core.models.allocations import ResourceType
 from krr_amd.core.packing import PackedFleet, PackedSeries, pack_resource, pod_view
 from krr_amd.utils.prom_decimal import prom_decimal
 
-__all__ = ["FleetBatch", "FleetExceedance", "FleetMoments", "FleetOverlay", "FleetProfile", "FleetRollup",
-           "FleetStats", "allocation_thresholds", "decay_weights", "window_weights"]
+__all__ = ["FleetBatch", "FleetExceedance", "FleetHistogram", "FleetMoments", "FleetOverlay", "FleetProfile",
+           "FleetRollup", "FleetStats", "HistogramBins", "allocation_thresholds", "decay_weights", "default_bins",
+           "window_weights"]
 
 
 @dataclass
@@ -628,6 +630,187 @@ def window_weights(last: int, length: int) -> np.ndarray:
     return w
 
 
+_QNAN_BITS = np.uint64(0x7FF8000000000000)
+
+
+def _okeys(values: np.ndarray) -> np.ndarray:
+    """uint64: the kernels' order-preserving key of every float64's bits (-0.0 below +0.0)."""
+    u = np.ascontiguousarray(values, dtype=np.float64).view(np.uint64)
+    return np.where(u >> np.uint64(63) != 0, ~u, u | np.uint64(1 << 63))
+
+
+@dataclass(frozen=True)
+class HistogramBins:
+    """The data-independent log-linear bins of ``FleetBatch.histogram`` (krr_sketch_params):
+    every octave [2^E, 2^(E+1)) from E = ``min_exponent`` up, ``octaves`` of them, is cut into
+    2^``mantissa_bits`` equal bins, so a bin's relative width is at most 2^-mantissa_bits.  A row
+    has ``width`` = nbins + 4 words: [0] negative, [1] +-0, [2] (0, 2^min_exponent),
+    [3 .. 3 + nbins) the log-linear bins, [3 + nbins] everything from 2^(min_exponent + octaves)
+    up, +Inf included.  A sample's bin comes from its bits alone, so two histograms with equal
+    bins add word for word.  ValueError outside 0 <= mantissa_bits <= 10, octaves >= 1,
+    min_exponent >= -1022, min_exponent + octaves <= 1024 and width <= 4096."""
+    mantissa_bits: int
+    min_exponent: int
+    octaves: int
+
+    def __post_init__(self):
+        for name in ("mantissa_bits", "min_exponent", "octaves"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an int, got {v!r}")
+            object.__setattr__(self, name, int(v))
+        m, e, o = self.mantissa_bits, self.min_exponent, self.octaves
+        if not 0 <= m <= 10 or o < 1 or e < -1022 or e + o > 1024:
+            raise ValueError(f"bins outside 0 <= mantissa_bits <= 10, octaves >= 1, min_exponent >= -1022, "
+                             f"min_exponent + octaves <= 1024: {self!r}")
+        if self.width > 4096:
+            raise ValueError(f"a histogram row holds at most 4096 words, these bins need {self.width}")
+
+    @property
+    def nbins(self) -> int:
+        return self.octaves << self.mantissa_bits
+
+    @property
+    def width(self) -> int:
+        return self.nbins + 4
+
+    def params(self) -> _native.KrrSketchParams:
+        return _native.KrrSketchParams(self.mantissa_bits, self.min_exponent, self.octaves, 0)
+
+    def edges(self) -> np.ndarray:
+        """float64 [nbins + 1], exact: entry i is the lower edge of row word 3 + i,
+        2^E (1 + j 2^-m) with E = min_exponent + (i >> m) and j = i & (2^m - 1); the last entry
+        is 2^(min_exponent + octaves), where the top word starts (+Inf when that is 2^1024)."""
+        base = (self.min_exponent + 1023) << self.mantissa_bits
+        u = (np.arange(self.nbins + 1, dtype=np.uint64) + np.uint64(base)) << np.uint64(52 - self.mantissa_bits)
+        return u.view(np.float64)
+
+    def bin_of(self, values) -> np.ndarray:
+        """int64, the shape of ``values``: the row word every float64 falls into, by the kernels'
+        rule on its bits; -1 for a NaN."""
+        x = np.asarray(values, dtype=np.float64)
+        u = np.ascontiguousarray(x).view(np.uint64).reshape(x.shape)
+        mag = u & np.uint64((1 << 63) - 1)
+        i = (mag >> np.uint64(52 - self.mantissa_bits)).astype(np.int64) - ((self.min_exponent + 1023)
+                                                                              << self.mantissa_bits)
+        b = np.where((i >= 0) & (i < self.nbins), 3 + i, np.where(i < 0, 2, 3 + self.nbins))
+        b = np.where(u >> np.uint64(63) != 0, 0, b)
+        b = np.where(mag == 0, 1, b)
+        return np.where(np.isnan(x), -1, b).astype(np.int64)
+
+
+def default_bins(resource: ResourceType) -> HistogramBins:
+    """The bins ``FleetBatch.histogram`` takes when none are given: 16 per octave (a relative bin
+    width of at most 6.25%) over 2^-10 .. 2^10 cores for CPU and 2^20 .. 2^40 bytes for memory,
+    324 words a row either way.  (Kubernetes VPA's buckets grow by 5% over 0.01 .. 1000 cores and
+    10 MB .. 1 TB.)"""
+    return HistogramBins(4, -10, 20) if ResourceType(resource) == ResourceType.CPU else HistogramBins(4, 20, 20)
+
+
+class FleetHistogram:
+    """Every object's histogram of weights (``FleetBatch.histogram``): the rows stay in HBM, and
+    any number of percentiles is read from them without touching the samples again.
+
+    ``count`` (int64) and ``flags`` (uint32) are krr_segmented_stats'; ``wsum`` (uint64) is a
+    row's total weight W and ``total`` = W / 2^32 the effective sample count under
+    ``decay_weights``; ``wmin`` / ``wmax`` (float64) are the least and greatest sample of positive
+    weight, NaN where W == 0.  All [S], host arrays.
+
+    A percentile's answer is a BIN: the one that holds ``FleetBatch.weighted_percentile``'s exact
+    answer for the same table (the rule is the same and a sample's bin never decreases with its
+    value).  ``bracket(p)`` is that bin's range clamped to [wmin, wmax], and ``percentile(p)`` its
+    upper end, VPA's "end of the bucket": never below the exact weighted percentile and, inside
+    the log-linear bins, at most (1 + 2^-mantissa_bits) times it.  Below 2^min_exponent and from
+    2^(min_exponent + octaves) up the bracket is as wide as the data (KRR_FLAG_SKETCH_RANGE).
+
+    Rows are integers, so ``merge`` is exact in any order: time slices of the same objects (the
+    older one built with ``age_base`` = the slots that follow it) and the shards of other ranks
+    add up to the histogram of the whole.  A decayed histogram cannot be AGED after the fact:
+    integer weights do not rescale exactly, so a later "now" needs a rebuild or ``age_base``."""
+
+    def __init__(self, resource, bins: HistogramBins, hist, count, flags, wsum, wmin, wmax, device: int, engine):
+        self.resource, self.bins = resource, bins
+        self._hist = hist
+        self.count, self.flags = count, flags
+        self.wsum, self.wmin, self.wmax = wsum, wmin, wmax
+        self.device, self._engine = device, engine
+        self._answers: dict = {}
+
+    @property
+    def n_objects(self) -> int:
+        return int(self.count.size)
+
+    @property
+    def total(self) -> np.ndarray:
+        return self.wsum.astype(np.float64) / float(WEIGHT_MAX)
+
+    def tensor(self):
+        """The rows in HBM: an int64 tensor [S, bins.width] of uint64 words below 2^63."""
+        return self._hist
+
+    def of(self, s: int) -> np.ndarray:
+        """uint64 [bins.width]: object s's row on the host."""
+        return self._hist[int(s)].cpu().numpy().view(np.uint64)
+
+    def _query(self, percentiles) -> dict:
+        fracs = tuple(percentile_fraction(p) for p in percentiles)
+        missing = {f: p for f, p in zip(fracs, percentiles) if f not in self._answers}  # asked once each
+        if missing:
+            r = self._engine.whist_query(self._hist, self.wmin, self.wmax, self.bins.params(), list(missing.values()))
+            for j, f in enumerate(missing):
+                self._answers[f] = {k: v[j] for k, v in r.items()}
+        return {k: np.stack([self._answers[f][k] for f in fracs]) for k in ("bin", "lower", "upper", "flags")}
+
+    def percentiles(self, percentiles: Sequence, return_flags: bool = False):
+        """float64 [P, S]: row j is the upper end of the bracket of ``percentiles[j]`` (anything
+        ``weighted_percentile`` takes), all read from the rows in one launch per
+        KRR_MAX_PERCENTILES of them; NaN where an object has no weight.  ``return_flags``: also
+        uint32 [P, S], the object's KRR_FLAG_NAN / KRR_FLAG_EMPTY joined with the answer's
+        KRR_FLAG_EMPTY (no weight) and KRR_FLAG_SKETCH_RANGE (a lumped bin)."""
+        percentiles = list(percentiles)
+        if not percentiles:
+            raise ValueError("at least one percentile")
+        r = self._query(percentiles)
+        return (r["upper"], r["flags"] | self.flags[None, :]) if return_flags else r["upper"]
+
+    def percentile(self, percentile, return_flags: bool = False):
+        """float64 [S]: ``percentiles([percentile])[0]``."""
+        r = self.percentiles([percentile], return_flags)
+        return (r[0][0], r[1][0]) if return_flags else r[0]
+
+    def bracket(self, percentile) -> tuple:
+        """(lower, upper), float64 [S] each: the range of the bin that holds the exact weighted
+        percentile, clamped to [wmin, wmax]; NaN where an object has no weight."""
+        r = self._query([percentile])
+        return r["lower"][0], r["upper"][0]
+
+    def answer_bins(self, percentile) -> np.ndarray:
+        """int32 [S]: the row word that answers ``percentile``, -1 where an object has no weight."""
+        return self._query([percentile])["bin"][0]
+
+    def merge(self, other: "FleetHistogram") -> "FleetHistogram":
+        """The histogram of both sets of samples, object by object: the rows and the total
+        weights add (exact, any order), the counts add, wmin / wmax are the least / greatest of
+        the two in sample order (NaN ignored), KRR_FLAG_EMPTY stays only where both were empty
+        and KRR_FLAG_NAN where either had it.  ValueError unless both have the same bins and
+        number of objects.  For two time slices of the same objects, build the OLDER one with
+        ``age_base`` = the newer one's slots."""
+        if not isinstance(other, FleetHistogram) or other.bins != self.bins or other.n_objects != self.n_objects:
+            raise ValueError("merge needs a FleetHistogram of the same bins and number of objects")
+
+        def pick(a, b, greatest):
+            ka, kb = _okeys(a), _okeys(b)
+            take_b = np.isnan(a) | (~np.isnan(b) & ((kb > ka) if greatest else (kb < ka)))
+            return np.where(take_b, b, a)
+
+        empty = np.uint32(_native.KRR_FLAG_EMPTY)
+        flags = ((self.flags | other.flags) & ~empty) | (self.flags & other.flags & empty)
+        return FleetHistogram(self.resource, self.bins, self._hist + other._hist.to(self._hist.device),
+                              self.count + other.count, flags.astype(np.uint32), self.wsum + other.wsum,
+                              pick(self.wmin, other.wmin, False), pick(self.wmax, other.wmax, True), self.device,
+                              self._engine)
+
+
 def _slots(ps: PackedSeries) -> np.ndarray:
     """int64 [S]: each series' length in slots, from the offsets wherever they live."""
     offs = ps.offsets
@@ -856,6 +1039,39 @@ class FleetBatch:
                     if len(k) == 4 and k[:2] == (resource, "wquantile") and k[3] == tab), None)
         r = hit if hit is not None else self._wquantile(resource, 100, weights)
         return r["wsum"].astype(np.float64) / float(WEIGHT_MAX)
+
+    def histogram(self, resource: ResourceType, weights=None, bins: Optional[HistogramBins] = None,
+                  age_base=0) -> FleetHistogram:
+        """Every object's histogram of weights over data-independent log-linear bins, from ONE
+        pass over the values (krr_segmented_whist): the form of the recency-weighted distribution
+        that gives any number of percentiles without another pass and that merges exactly, at the
+        price of a value error of one bin.  ``weights`` is an age-indexed table as
+        ``weighted_percentile`` takes it (None: the unit table, a plain histogram); ``bins`` a
+        ``HistogramBins`` (None: ``default_bins(resource)``); ``age_base`` an int or an int64
+        array [S], not negative: the slots that FOLLOW each object's series when this batch holds
+        an older slice of it, so that the slice's ``FleetHistogram`` merges with the newer one's
+        into the histogram of the whole.  Cached per (resource, bins, weight bytes, age_base
+        bytes).  Works on a ``per_pod()`` view unchanged (a row per pod).  On series packed
+        without gaps age counts SAMPLES, as for ``weighted_percentile``."""
+        resource = ResourceType(resource)
+        bins = default_bins(resource) if bins is None else bins
+        if not isinstance(bins, HistogramBins):
+            raise ValueError(f"bins must be a HistogramBins, got {bins!r}")
+        tab = weight_table(np.array([1], dtype=np.uint64) if weights is None else weights)
+        ps = self.series(resource)
+        if isinstance(age_base, bool) or (np.ndim(age_base) == 0 and not isinstance(age_base, (int, np.integer))):
+            raise ValueError(f"age_base must be an int or an int64 array, got {age_base!r}")
+        base = np.asarray(age_base)
+        if not np.issubdtype(base.dtype, np.integer) or (base < 0).any() or base.shape not in ((), (ps.n_segments,)):
+            raise ValueError(f"age_base must be a non-negative int or an int64 array [{ps.n_segments}]")
+        base = np.ascontiguousarray(np.broadcast_to(base.astype(np.int64), (ps.n_segments,)))
+        key = (resource, "histogram", bins, tab.tobytes(), base.tobytes())
+        h = self._cache.get(key)
+        if h is None:
+            r = self.engine.whist_series(ps, tab, bins.params(), base if base.any() else None)
+            h = self._cache[key] = FleetHistogram(resource, bins, r["hist"], r["count"], r["flags"], r["wsum"],
+                                                  r["wmin"], r["wmax"], self.device, self.engine)
+        return h
 
     def percentiles(self, resource: ResourceType, percentiles: Sequence, mode: str = "ref_index",
                     return_flags: bool = False):

@@ -422,6 +422,71 @@ class SimpleEngine:
         host["wsum"] = host["wsum"].view(np.uint64)
         return host
 
+    def whist_series(self, ps: PackedSeries, weights, bins: _native.KrrSketchParams, age_base=None) -> dict:
+        """Per segment a histogram of age-indexed integer weights over the log-linear bins
+        ``bins``, from one pass (krr_segmented_whist): ``hist``, an int64 tensor [S, width] LEFT
+        IN HBM (uint64 words below 2^63: rows add exactly with a tensor add), and the host arrays
+        ``wsum`` (uint64), ``wmin`` / ``wmax`` (float64: the least and greatest sample of
+        positive weight, NaN without one), ``count`` (int64) and ``flags`` (uint32), [S] each.
+        ``weights`` as ``wquantile_series`` takes it; ``age_base`` None or int64 [S], not
+        negative: the slots that FOLLOW each segment in the series it is a slice of.  The table
+        is uploaded once; chunks and synchronisation as ``stats_series``, a chunk taking the
+        ``age_base`` of its own segment range."""
+        import torch
+
+        tab = weight_table(weights)
+        base = None
+        if age_base is not None:
+            base = np.ascontiguousarray(age_base, dtype=np.int64)
+            if base.shape != (ps.n_segments,) or (base < 0).any():
+                raise ValueError(f"age_base must be int64 [{ps.n_segments}] and not negative")
+        ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        width = ctx.sketch_width(bins)
+        parts, d_tab, lo = [], None, 0
+        for part in self._series_parts(ps):
+            if d_tab is None:
+                d_tab = self._upload_table(tab)
+            hi = lo + part.n_segments
+            parts.append(self._whist_part(ctx, part, d_tab, bins, width, None if base is None else base[lo:hi]))
+            lo = hi
+        host = self._host_concat([{k: v for k, v in p.items() if k != "hist"} for p in parts],
+                                 {"wsum": np.int64, "wmin": np.float64, "wmax": np.float64, "count": np.int64,
+                                  "flags": np.int32})
+        host["wsum"] = host["wsum"].view(np.uint64)
+        if len(parts) == 1:
+            host["hist"] = parts[0]["hist"]
+        elif parts:
+            host["hist"] = torch.cat([p["hist"] for p in parts], dim=0)
+        else:
+            host["hist"] = torch.empty((0, width), dtype=torch.int64, device=torch.device("cuda", self.device))
+        return host
+
+    def whist_query(self, rows, wmin, wmax, bins: _native.KrrSketchParams, percentiles) -> dict:
+        """Percentiles read from histogram rows (krr_whist_query): host arrays ``bin`` (int32: the
+        answer bin, -1 for a row without weight), ``lower`` / ``upper`` (float64: the bin's range
+        clamped to [wmin, wmax]) and ``flags`` (uint32), [P, R] each, row j for
+        ``percentiles[j]`` (anything ``percentile_fraction`` takes).  ``rows`` is an int64 tensor
+        [R, width] in HBM, ``wmin`` / ``wmax`` float64 [R], host arrays or tensors.  Lists longer
+        than KRR_MAX_PERCENTILES run in groups; one synchronisation at the end."""
+        import torch
+
+        fracs = [percentile_fraction(p) for p in percentiles]
+        if not fracs:
+            raise ValueError("at least one percentile")
+        ctx = self.context()
+        dev = torch.device("cuda", self.device)
+        R, P, G = int(rows.shape[0]), len(fracs), _native.KRR_MAX_PERCENTILES
+        with torch.cuda.device(self.device):
+            mn, mx = (t.to(dev) if isinstance(t, torch.Tensor)
+                      else torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64)).to(dev) for t in (wmin, wmax))
+            out = self._outputs((("bin", torch.int32, P), ("lower", torch.float64, P), ("upper", torch.float64, P),
+                                 ("flags", torch.int32, P)), R)
+            for a in range(0, P, G):
+                ctx.whist_query(rows, mn, mx, bins, fracs[a:a + G], out["bin"][a:a + G], out["lower"][a:a + G],
+                                out["upper"][a:a + G], out["flags"][a:a + G])
+        return self._host_concat([out], {"bin": np.int32, "lower": np.float64, "upper": np.float64,
+                                         "flags": np.int32})
+
     def rollup_series(self, ps: PackedSeries, window: int, align: int) -> dict:
         """Every segment of one series cut into windows of ``window`` slots
         (krr_segmented_rollup; ``align`` KRR_ROLLUP_START or KRR_ROLLUP_END): ``wcount`` (int32),
@@ -680,6 +745,23 @@ class SimpleEngine:
                                  ("count", torch.int64, 0), ("flags", torch.int32, 0)), part.n_segments)
             ctx.segmented_wquantile(series, table, p_num, p_den, out["value"], out["wsum"], out["passes"],
                                     out["count"], out["flags"])
+        return out
+
+    def _whist_part(self, ctx, part: PackedSeries, table, bins, width: int, age_base) -> dict:
+        """Upload (host series, and the chunk's ``age_base`` when there is one) and one
+        krr_segmented_whist launch on the current stream with the weight table ``table`` (int64
+        storage, already on the device): the chunk's device tensors, ``hist`` [n, width]."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(self.device):
+            series = self._part_series(ctx, part)
+            base = None if age_base is None else torch.from_numpy(np.array(age_base, dtype=np.int64)).to(dev)
+            out = self._outputs((("wsum", torch.int64, 0), ("wmin", torch.float64, 0), ("wmax", torch.float64, 0),
+                                 ("count", torch.int64, 0), ("flags", torch.int32, 0)), part.n_segments)
+            out["hist"] = torch.empty((part.n_segments, width), dtype=torch.int64, device=dev)
+            ctx.segmented_whist(series, bins, table, base, out["hist"], out["wsum"], out["wmin"], out["wmax"],
+                                out["count"], out["flags"])
         return out
 
     def _resident(self, part: PackedSeries) -> PackedSeries:

@@ -4456,6 +4456,209 @@ __global__ __launch_bounds__(64) void k_wquantile(WqArgs A) {
     }
 }
 
+// ------------------------------ WHIST --------------------------------------
+// krr_segmented_whist / krr_whist_query: per segment a histogram of 64-bit integer WEIGHTS over
+// the sketch's data-independent log-linear bins, from ONE pass (krr_amd.h states the rule).  It
+// joins two things that exist above: sketch_bin takes a sample's bin straight from its bits (no
+// table of edges, no transcendental, monotone in okey), and WqTable / SegCursor give a slot's age
+// and weight.  Rows of integers add exactly and in any order, so the rows of time slices (built
+// with age_base = the slots that follow the slice) and of ranks merge by a plain integer add.
+// THE RUN IN HAND.  A memory series sits in one or two bins, and 64 lanes adding to one LDS word
+// serialise.  A lane therefore keeps (bin, summed weight) of the run of equal bins it is in and
+// issues one 64-bit LDS atomic when the bin CHANGES (and once at the end): a lane whose 16 slots of
+// a chunk share a bin issues none.  Integer sums: regrouping cannot change a bit.
+// WEIGHTS ONE CHUNK AHEAD.  k_wquantile loads its weights inside the chunk body and waits for them
+// there, which also drains the skeleton's prefetch of the next chunk's values.  Here row u of a
+// chunk consumes the two weights loaded a call earlier and at once issues the loads of row u of
+// the NEXT chunk (its ages are known from the cursor): the loads waited for are always the oldest
+// in flight, and the newer value loads stay outstanding.  The loads issued during the last chunk
+// are never consumed; their addresses are clamped into the table like any other.
+// LDS: width x 8 B, dynamic (<= 32 KiB); the row is written once per segment.
+struct WhistProc {
+    WqTable T;  // moved by the segment's age_base
+    SegCursor at;
+    unsigned long long* h;
+    SketchGeom g;
+    uint64_t wn[2 * kUnroll];  // this lane's weights of the chunk to come
+    uint64_t w_l, kmn, kmx;    // per lane: weight, least and greatest key of positive weight
+    uint32_t nan_l;            // per lane: NaN slots (padding included)
+    uint32_t cb;               // the run in hand: its bin and summed weight
+    uint64_t cw;
+    __device__ __forceinline__ WhistProc(const WqTable& t, int64_t beg, int64_t end, int lane,
+                                         unsigned long long* h_, const SketchGeom& g_)
+        : T(t), at(seg_geom(beg, end), lane), h(h_), g(g_), w_l(0), kmn(~0ull), kmx(0), nan_l(0), cb(~0u), cw(0) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) T.weights(at, u, wn[2 * u], wn[2 * u + 1]);
+    }
+    __device__ __forceinline__ void slot(double d, uint64_t w) {
+        const uint64_t x = dbits(d), key = okey(x);
+        const bool nan = is_nan_bits(x);
+        w = nan ? 0ull : w;
+        nan_l += nan ? 1u : 0u;
+        w_l += w;
+        if (w) {
+            kmn = key < kmn ? key : kmn;
+            kmx = key > kmx ? key : kmx;
+            const uint32_t b = sketch_bin(g, x);
+            if (b != cb) {
+                if (cw) atomicAdd(&h[cb], (unsigned long long)cw);
+                cb = b;
+                cw = 0;
+            }
+            cw += w;
+        }
+    }
+    __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
+        SegCursor nx = at;
+        nx.next();
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const uint64_t wx = wn[2 * u], wy = wn[2 * u + 1];
+            T.weights(nx, u, wn[2 * u], wn[2 * u + 1]);
+            slot(c[u].x, wx);
+            slot(c[u].y, wy);
+        }
+        at = nx;
+    }
+    __device__ __forceinline__ void flush() {
+        if (cw) atomicAdd(&h[cb], (unsigned long long)cw);
+        cw = 0;
+    }
+};
+
+struct WhistArgs {
+    SeriesArgs h;
+    SketchGeom g;
+    const uint64_t* tab;
+    int64_t nw;
+    const int64_t* age_base;  // may be null: all 0
+    uint64_t* out_h;          // [S][width]
+    uint64_t* out_w;          // may be null
+    double* out_mn;           // may be null
+    double* out_mx;           // may be null
+};
+
+__global__ __launch_bounds__(64) void k_whist(WhistArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long* h = reinterpret_cast<unsigned long long*>(smem);
+    const int lane = threadIdx.x;
+    for (int64_t bi = blockIdx.x; bi < A.h.S; bi += gridDim.x) {
+        const auto [s, beg, end] = series_item(A.h, bi);
+        const uint64_t L = (uint64_t)(end - beg);
+        for (uint32_t i = lane; i < A.g.width; i += kWave) h[i] = 0;
+        __syncthreads();
+        // age a + age_base reads tab[min(a + base, nw - 1)]: the table moved by min(base, nw - 1) entries
+        const int64_t ab = clamp_i64(A.age_base ? A.age_base[s] : 0, 0, A.nw - 1);
+        WhistProc P(WqTable{A.tab + ab, A.nw - ab, (int64_t)L}, beg, end, lane, h, A.g);
+        const uint32_t pad = stream_segment<true>(A.h.vals, beg, end, P, lane);
+        P.flush();
+        __syncthreads();
+        const uint64_t nnan = wave_sum_u32(P.nan_l) - pad;
+        const SeriesCount sc = series_count(A.h, L, L - nnan);
+        const bool bad = sc.flags & KRR_FLAG_NAN;
+        const uint64_t W = bad ? 0ull : wave_sum_u64(P.w_l);
+        const uint64_t mn = wave_min_u64(P.kmn), mx = wave_max_u64(P.kmx);
+        uint64_t* row = A.out_h + (size_t)s * A.g.width;
+        for (uint32_t i = lane; i < A.g.width; i += kWave) row[i] = bad ? 0ull : h[i];
+        if (lane == 0) {
+            if (A.out_w) A.out_w[s] = W;
+            if (A.out_mn) A.out_mn[s] = bitsd(W ? okey_inv(mn) : kQuietNaN);
+            if (A.out_mx) A.out_mx[s] = bitsd(W ? okey_inv(mx) : kQuietNaN);
+            sc.write(A.h, s);
+        }
+        __syncthreads();
+    }
+}
+
+// The value range [lo, hi] (bit patterns) of bin b of a row whose least and greatest positive-weight
+// samples are mn and mx: the bin's edges, built from powers of two in the bits themselves, clamped
+// by okey order.  The lumped bins 0, 2 and the top one set KRR_FLAG_SKETCH_RANGE.
+__device__ __forceinline__ void whist_range(const SketchGeom& g, uint32_t b, uint64_t mn, uint64_t mx, uint64_t& lo,
+                                            uint64_t& hi, uint32_t& flags) {
+    auto omax = [](uint64_t a, uint64_t c) { return okey(a) < okey(c) ? c : a; };
+    auto omin = [](uint64_t a, uint64_t c) { return okey(c) < okey(a) ? c : a; };
+    const uint32_t sh = 52u - g.m;
+    if (b == 1) {  // +-0
+        lo = hi = 0ull;
+    } else if (b == 0) {  // negatives: [wmin, -0.0]
+        lo = mn;
+        hi = omin(kSignBit, mx);
+        flags |= KRR_FLAG_SKETCH_RANGE;
+    } else if (b == 2) {  // (0, 2^e_lo)
+        lo = omax(0ull, mn);
+        hi = omin(g.low_bits, mx);
+        flags |= KRR_FLAG_SKETCH_RANGE;
+    } else if (b == 3 + g.nbins) {  // [2^(e_lo + octaves), wmax]
+        lo = omax((uint64_t)(g.base + g.nbins) << sh, mn);
+        hi = mx;
+        flags |= KRR_FLAG_SKETCH_RANGE;
+    } else {  // bin 3 + i: the edges are the bit patterns (base + i) << sh and (base + i + 1) << sh
+        const uint32_t i = b - 3;
+        lo = omax((uint64_t)(g.base + i) << sh, mn);
+        hi = omin((uint64_t)(g.base + i + 1) << sh, mx);
+    }
+}
+
+struct WhistQueryArgs {
+    int64_t S;
+    SketchGeom g;
+    const uint64_t* hist;
+    const double* wmin;
+    const double* wmax;
+    int32_t n;  // percentiles in use, 1 .. KRR_MAX_PERCENTILES
+    uint64_t p_num[KRR_MAX_PERCENTILES], den[KRR_MAX_PERCENTILES];  // den = 100 * p_den
+    int32_t* out_b;  // row-major [n][S], as the three below
+    double* out_lo;
+    double* out_hi;
+    uint32_t* out_f;
+};
+
+// One wave per row: lane l sums bins [per l, per l + per), a scan finds the lane whose share holds
+// the answer, a second scan over that share the bin (per <= kWave: width <= 4096).
+__global__ __launch_bounds__(64) void k_whist_query(WhistQueryArgs A) {
+    const int lane = threadIdx.x;
+    const uint32_t width = A.g.width, per = (width + kWave - 1) / kWave;
+    for (int64_t s = blockIdx.x; s < A.S; s += gridDim.x) {
+        const uint64_t* row = A.hist + (size_t)s * width;
+        const uint32_t b0 = (uint32_t)lane * per;
+        uint64_t t = 0;
+        for (uint32_t j = 0; j < per; ++j) t += b0 + j < width ? row[b0 + j] : 0ull;
+        const uint64_t incl = wave_scan64(t, 0ull, OpAdd64{});
+        const uint64_t W = lane_bcast64(incl, kWave - 1);
+        const uint64_t mn = dbits(A.wmin[s]), mx = dbits(A.wmax[s]);
+#pragma unroll 1
+        for (int32_t q = 0; q < A.n; ++q) {
+            int32_t bin = -1;
+            uint64_t lo = kQuietNaN, hi = kQuietNaN;
+            uint32_t flags = KRR_FLAG_EMPTY;
+            const unsigned __int128 target = (unsigned __int128)W * A.p_num[q];
+            const uint64_t den = A.den[q];
+            const uint64_t m = ballot(wq_reached(incl, den, target));  // p <= 100: the last lane reaches it
+            if (W && m) {
+                const int src = __ffsll((long long)m) - 1;
+                const uint64_t base = lane_bcast64(incl - t, src);
+                const uint32_t idx = (uint32_t)src * per + (uint32_t)lane;
+                const bool mine = (uint32_t)lane < per && idx < width;
+                const uint64_t hb = mine ? row[idx] : 0ull;
+                const uint64_t incl2 = wave_scan64(hb, 0ull, OpAdd64{});
+                const uint64_t m2 = ballot(mine && wq_reached(base + incl2, den, target));
+                if (m2) {
+                    bin = (int32_t)((uint32_t)src * per) + __ffsll((long long)m2) - 1;
+                    flags = 0;
+                    whist_range(A.g, (uint32_t)bin, mn, mx, lo, hi, flags);
+                }
+            }
+            if (lane == 0) {
+                const size_t o = (size_t)q * (size_t)A.S + (size_t)s;
+                A.out_b[o] = bin;
+                A.out_lo[o] = bitsd(lo);
+                A.out_hi[o] = bitsd(hi);
+                A.out_f[o] = flags;
+            }
+        }
+    }
+}
+
 }  // namespace krr
 #include "krr_kll.h"
 namespace krr {
@@ -5258,6 +5461,67 @@ int krr_segmented_wquantile(krr_ctx* ctx, const krr_series* series, const uint64
         hipLaunchKernelGGL(k_wquantile, grid, dim3(64), 0, (hipStream_t)stream, A);
         return KRR_OK;
     });
+}
+
+constexpr int64_t kWhistMaxWidth = 4096;  // 32 KiB of LDS per wave; k_whist_query's share per lane <= kWave bins
+
+int krr_segmented_whist(krr_ctx* ctx, const krr_series* series, const krr_sketch_params* bins,
+                        const uint64_t* age_weights, int64_t n_weights, const int64_t* age_base, uint64_t* out_hist,
+                        uint64_t* out_wsum, double* out_wmin, double* out_wmax, int64_t* out_count,
+                        uint32_t* out_flags, void* stream) {
+    return series_entry(ctx, series, out_count, out_flags, KRR_OK, [&](const SeriesArgs& H, dim3 grid) -> int {
+        const int64_t width = krr_sketch_width(bins);
+        if (width < 0) return set_err(ctx, KRR_E_INVALID, "bad histogram bins%s", "");
+        if (width > kWhistMaxWidth)
+            return set_err(ctx, KRR_E_UNSUPPORTED, "histogram width %s%lld above 4096", "", (long long)width);
+        if (!age_weights || n_weights < 1)
+            return set_err(ctx, KRR_E_INVALID, "null age_weights or n_weights < 1%s: %lld", "", (long long)n_weights);
+        if (!out_hist || !out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null outputs%s", "");
+        const WhistArgs A{H, sketch_geom(*bins), age_weights, n_weights, age_base, out_hist, out_wsum, out_wmin,
+                          out_wmax};
+        hipLaunchKernelGGL(k_whist, grid, dim3(64), (size_t)width * 8, (hipStream_t)stream, A);
+        return KRR_OK;
+    });
+}
+
+int krr_whist_query(krr_ctx* ctx, int64_t n_rows, const krr_sketch_params* bins, const uint64_t* hist,
+                    const double* wmin, const double* wmax, const int64_t* p_num, const int64_t* p_den,
+                    int32_t n_percentiles, int32_t* out_bin, double* out_lower, double* out_upper,
+                    uint32_t* out_flags, void* stream) {
+    if (!ctx) return KRR_E_INVALID;
+    const int64_t width = krr_sketch_width(bins);
+    if (width < 0) return set_err(ctx, KRR_E_INVALID, "bad histogram bins%s", "");
+    if (width > kWhistMaxWidth)
+        return set_err(ctx, KRR_E_UNSUPPORTED, "histogram width %s%lld above 4096", "", (long long)width);
+    if (n_rows < 0) return set_err(ctx, KRR_E_INVALID, "negative n_rows%s", "");
+    if (n_percentiles < 1 || n_percentiles > KRR_MAX_PERCENTILES || !p_num || !p_den)
+        return set_err(ctx, KRR_E_INVALID, "n_percentiles must be in [1, KRR_MAX_PERCENTILES], got %s%lld", "",
+                       (long long)n_percentiles);
+    WhistQueryArgs A{};
+    for (int32_t j = 0; j < n_percentiles; ++j) {
+        if (p_num[j] <= 0 || p_den[j] <= 0 || p_den[j] > 1000000000000000ll || p_num[j] > 100 * p_den[j])
+            return set_err(ctx, KRR_E_INVALID, "percentile outside (0, 100] or p_den > 10^15%s", "");
+        A.p_num[j] = (uint64_t)p_num[j];
+        A.den[j] = 100ull * (uint64_t)p_den[j];
+    }
+    if (n_rows == 0) return KRR_OK;
+    if (!hist || !wmin || !wmax || !out_bin || !out_lower || !out_upper || !out_flags)
+        return set_err(ctx, KRR_E_INVALID, "null pointers%s", "");
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return set_err(ctx, KRR_E_HIP, "cannot select device%s", "");
+    A.S = n_rows;
+    A.g = sketch_geom(*bins);
+    A.hist = hist;
+    A.wmin = wmin;
+    A.wmax = wmax;
+    A.n = n_percentiles;
+    A.out_b = out_bin;
+    A.out_lo = out_lower;
+    A.out_hi = out_upper;
+    A.out_f = out_flags;
+    hipLaunchKernelGGL(k_whist_query, dim3(grid_for(n_rows)), dim3(64), 0, (hipStream_t)stream, A);
+    KRR_HIP(ctx, hipGetLastError());
+    return KRR_OK;
 }
 
 int krr_segmented_rollup(krr_ctx* ctx, const krr_series* series, int64_t window, int32_t align,
