@@ -286,6 +286,60 @@ int krr_segmented_rollup(krr_ctx* ctx, const krr_series* series, int64_t window,
                          double* out_wsum, uint32_t* out_wcount, int64_t* out_count,
                          uint32_t* out_flags, void* stream);
 
+/* Per segment, ONE pass: the window of `window` slots that ENDS at every slot, with count, min,
+ * max, sum and mean per slot, and per segment the largest of those means — the sustained peak
+ * ("the highest load held for any W consecutive slots"; krr_amd.api.FleetSliding).  A rollup's
+ * windows lie on one grid and split a burst that straddles a boundary; these do not.
+ * For segment s with L = offsets[s+1] - offsets[s] slots and W = window:
+ *   - slot i's window is slots [max(0, i - W + 1), i]; P = its present slots: every slot, or the
+ *     non-NaN slots when gaps_are_nan; c = |P|;
+ *   - the window is EMITTED iff c >= min_count;
+ *   - slot i is written at index offsets[s] + i of each per-slot output ([n_values]): the output
+ *     offsets are the series' own, there is no capacity case.
+ * Per slot:
+ *   wcount  = c, always
+ *   min, max = an extremal sample's own bits under float comparison, an extremum of zero as +0.0
+ *   sum     = a plain IEEE float64 sum of P, the window's own samples only, in one fixed order,
+ *             uncompensated: within (c-1) u / (1 - (c-1) u) x sum|x| of the exact sum, u = 2^-53,
+ *             whatever precedes the window (no difference of running sums)
+ *   mean    = fl(sum / c) of that sum, one IEEE division
+ *   a window that is not emitted: min = max = sum = mean = the quiet NaN 0x7FF8000000000000, so
+ *   every per-slot double output is a gapped series as it stands;
+ *   - an emitted window that holds a NaN sample in the compact layout (gaps_are_nan == 0): min =
+ *     max = sum = mean = the quiet NaN; the segment gets KRR_FLAG_NAN, other windows are unaffected;
+ *   - +-Inf: plain IEEE, no flag; a sum or mean that comes out NaN (+Inf and -Inf in one window)
+ *     is written as the quiet NaN.
+ * Per segment:
+ *   out_peak      = the largest emitted mean, zero as +0.0; the quiet NaN when no window is emitted
+ *                   or when ANY emitted mean is NaN (a poisoned compact window, Inf - Inf)
+ *   out_peak_slot = the first slot whose mean compares equal to the peak; -1 when no window is
+ *                   emitted; the first slot with a NaN mean when the peak is NaN for that reason
+ *   Both need no per-slot output: with those NULL the launch is a pure read.
+ * out_count, out_flags ([n_segments]): bit-identical to krr_segmented_stats on the same series.
+ * The same buffers give the same bits on every launch (no atomics); the order of a window's
+ * additions depends on W, on where the window lies in the W-slot blocks counted from slot 0 and in
+ * the kernel's steps (hence on the parity of the segment's start offset); no output's bits depend
+ * on which other outputs are NULL.
+ * Every per-slot and per-segment data output may be NULL and is then not written.
+ * KRR_E_INVALID: a null ctx or series; window outside 1..KRR_SLIDE_MAX_WINDOW; min_count outside
+ * 1..window; out_count or out_flags NULL while n_segments > 0.  n_segments == 0 launches nothing.
+ * One wave per segment, one read of every value; no atomics.  Windows of up to 24 slots are
+ * folded slot by slot from an LDS copy of the last window + 63 slots (the sum in slot order);
+ * longer ones are the suffix of one block of `window` slots and the prefix of the next, blocks
+ * counted from slot 0 (van Herk / Gil-Werman), each kept by a scan.  LDS per wave: 8,224 bytes
+ * of staging plus, for window > 24, 36 bytes per slot of `window` (raw slot, suffix sum, suffix
+ * min, suffix max, packed counts), 20 without out_min and out_max.  KRR_SLIDE_MAX_WINDOW keeps
+ * that within the 64 KiB a workgroup gets without opting in: 8,224 + 36 x 1,536 = 63,520.  What
+ * it costs in occupancy: a CU's 160 KiB hold 16 such waves at small windows (the registers' limit;
+ * 9 KiB of LDS each), 4 at window = 1,440 without min / max (37,024 bytes) and 2 with them
+ * (60,064 bytes), where the skeleton's kernels without LDS run 16 to 32.
+ * Segments of fewer than 2^32 slots, as krr_segmented_stats. */
+#define KRR_SLIDE_MAX_WINDOW 1536
+int krr_segmented_slide(krr_ctx* ctx, const krr_series* series, int64_t window, int64_t min_count,
+                        double* out_mean, double* out_sum, double* out_max, double* out_min,
+                        uint32_t* out_wcount, double* out_peak, int64_t* out_peak_slot,
+                        int64_t* out_count, uint32_t* out_flags, void* stream);
+
 /* Per object, ONE pass: its pods folded slot by slot into one series — the workload's total over
  * time (sum by (workload)), the replica count over time and the busiest-pod envelope
  * (krr_amd.api.FleetOverlay).  `pods` holds one segment per pod, as for krr_simple_run_pods; object

@@ -64,6 +64,7 @@ EXPORTED_SYMBOLS = (
     "krr_segmented_whist",
     "krr_whist_query",
     "krr_segmented_rollup",
+    "krr_segmented_slide",
     "krr_pods_overlay",
     "krr_simple_run",
     "krr_simple_run_records",
@@ -242,6 +243,7 @@ KRR_MAX_PERCENTILES = 4
 KRR_MAX_THRESHOLDS = 4  # krr_segmented_exceed: thresholds per launch
 KRR_ROLLUP_START = 0  # krr_segmented_rollup: windows start with the series (the last may be partial)
 KRR_ROLLUP_END = 1    # ... or end with it (the first may be partial)
+KRR_SLIDE_MAX_WINDOW = 1536  # krr_segmented_slide: the largest window (its LDS stays within 64 KiB)
 KRR_OVERLAY_START = 0  # krr_pods_overlay: an object's pods start together
 KRR_OVERLAY_END = 1    # ... or end together
 
@@ -321,6 +323,8 @@ def load_library(require_torch: bool = True) -> ctypes.CDLL:
         lib.krr_whist_query.restype = ctypes.c_int
         lib.krr_segmented_rollup.argtypes = [vp, sp, i64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_segmented_rollup.restype = ctypes.c_int
+        lib.krr_segmented_slide.argtypes = [vp, sp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.krr_segmented_slide.restype = ctypes.c_int
         lib.krr_pods_overlay.argtypes = [vp, sp, vp, i64, ctypes.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.krr_pods_overlay.restype = ctypes.c_int
         lib.krr_simple_run.argtypes = [vp, sp, sp, pp, vp, vp, vp, vp, vp, vp, vp]
@@ -656,6 +660,29 @@ class Context:
         self._check(self._lib.krr_segmented_rollup(
             self._h, ctypes.byref(series), int(window), int(align), win_offsets.data_ptr(),
             *(None if t is None else t.data_ptr() for t in (wmin, wmax, wsum, wcount)),
+            count.data_ptr(), flags.data_ptr(), self._stream(stream)))
+
+    def segmented_slide(self, series: KrrSeries, window: int, min_count: int, mean, wsum, wmax, wmin, wcount, peak,
+                        peak_slot, count, flags, stream=None) -> None:
+        """The window of ``window`` slots that ends at every slot, from one pass
+        (krr_segmented_slide): ``mean`` / ``wsum`` / ``wmax`` / ``wmin`` (float64) and ``wcount``
+        (int32 storage, read as uint32) are flat per-slot outputs of ``series.n_values`` entries
+        laid out by the series' own offsets, a window with fewer than ``min_count`` present slots
+        being the quiet NaN in the float outputs; ``peak`` (float64 [S]) is the largest emitted
+        mean of each segment and ``peak_slot`` (int64 [S]) its first slot.  Each of those is
+        optional (None: not written).  ``count`` int64 [S] and ``flags`` int32 [S] are required."""
+        for t, dt in ((mean, "float64"), (wsum, "float64"), (wmax, "float64"), (wmin, "float64"), (wcount, "int32")):
+            if t is not None:
+                _check_tensor(t, dt, series.n_values)
+        if peak is not None:
+            _check_tensor(peak, "float64", series.n_segments)
+        if peak_slot is not None:
+            _check_tensor(peak_slot, "int64", series.n_segments)
+        _check_tensor(count, "int64", series.n_segments)
+        _check_tensor(flags, "int32", series.n_segments)
+        self._check(self._lib.krr_segmented_slide(
+            self._h, ctypes.byref(series), int(window), int(min_count),
+            *(None if t is None else t.data_ptr() for t in (mean, wsum, wmax, wmin, wcount, peak, peak_slot)),
             count.data_ptr(), flags.data_ptr(), self._stream(stream)))
 
     def pods_overlay(self, pods: KrrSeries, pod_groups, n_objects: int, align: int, out_offsets, osum, omax, omin,

@@ -429,8 +429,10 @@ class FleetRollup(_FlatPerObject):
         return batch
 
     def peak(self, stat: str = "mean") -> np.ndarray:
-        """float64 [S]: the largest window value of every object — with ``mean`` the sustained
-        peak (the highest ``window``-slot average); NaN without a present sample."""
+        """float64 [S]: the largest window value of every object — with ``mean`` the highest
+        ``window``-slot average on this window grid (a burst that straddles a grid boundary is
+        split over two windows: ``FleetBatch.sustained_peak`` looks at every alignment); NaN
+        without a present sample."""
         return self.as_batch(stat).stats(self.resource).max
 
     def fold(self, period: int) -> FleetProfile:
@@ -472,6 +474,97 @@ class FleetRollup(_FlatPerObject):
         mx = torch.where(none | bad, nan, mx)
         total = torch.where(bad, nan, total)
         return FleetProfile(count.cpu().numpy(), mn.cpu().numpy(), mx.cpu().numpy(), total.cpu().numpy())
+
+
+_SLIDE_SERIES_STATS = ("mean", "sum", "max", "min")
+_SLIDE_STATS = _SLIDE_SERIES_STATS + ("wcount",)
+
+
+class FleetSliding(_FlatPerObject):
+    """One resource of a fleet under a moving window: for every slot of every object's series the
+    ``window`` slots that END there, with the mean, sum, max and min of their present samples and
+    their count (one krr_segmented_slide pass; include/krr_amd.h has the rules).  A window with
+    fewer than ``min_count`` present slots is NaN in the four float stats: as a value of a gapped
+    series that is an absent slot, so every one of them is a series again.
+
+    The per-slot arrays are laid out by the series' own ``offsets`` (int64 [S + 1]; ``slots`` [S]
+    the series' lengths, both host) and live in HBM; only the ones named in ``FleetBatch.sliding``'s
+    ``stats=`` exist, and asking for another raises ValueError.  ``peak`` (float64 [S]) is every
+    object's largest window mean — the sustained peak, the highest load held for ``window``
+    consecutive slots wherever they lie, where a rollup's grid splits a burst that straddles one of
+    its boundaries — and ``peak_slot`` (int64 [S]) the first slot it ends at, -1 without a window;
+    both are always present.  An object with a NaN sample (KRR_FLAG_NAN) has a NaN peak, with the
+    first slot whose window holds the NaN.  ``count`` and ``flags`` ([S], host) are
+    ``FleetBatch.stats``' for the whole series.  ``dense`` is right-justified: fleets end "now".
+
+    Two slides of adjacent time slices cannot be merged: a window across the cut needs the older
+    slice's last ``window - 1`` samples, which neither result keeps.  There is no ``concat``; slide
+    the joined series instead."""
+    _STATS = _SLIDE_STATS
+    _COUNT = "wcount"
+    align = "end"
+
+    def __init__(self, resource, window: int, min_count: int, offsets, count, flags, peak, peak_slot, tensors,
+                 device: int = 0, engine: Optional[SimpleEngine] = None):
+        import torch
+
+        self.resource = ResourceType(resource)
+        self.window = int(window)
+        self.min_count = int(min_count)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        self.slots = np.diff(self.offsets)
+        self.count = np.asarray(count, dtype=np.int64)
+        self.flags = np.asarray(flags).astype(np.uint32)
+        self.peak = np.asarray(peak, dtype=np.float64)
+        self.peak_slot = np.asarray(peak_slot, dtype=np.int64)
+        self.device = int(device)
+        self._engine = engine
+        self._t = {self._stat(k): torch.as_tensor(t) for k, t in dict(tensors).items()}
+        n = int(self.offsets[-1]) if self.offsets.size else 0
+        if self.peak.size != self.slots.size or any(t.numel() != n for t in self._t.values()):
+            raise ValueError("offsets, peak and the per-slot arrays do not describe the same slots")
+        self._host: dict = {}
+        self._batches: dict = {}
+
+    @property
+    def stats(self) -> tuple:
+        """The per-slot stats this result holds."""
+        return tuple(k for k in _SLIDE_STATS if k in self._t)
+
+    def tensor(self, stat: str):
+        """The flat per-slot tensor of ``stat`` where the kernel left it (HBM): ``wcount`` int32,
+        the others float64.  ValueError if the stat was not asked for in ``stats=``."""
+        stat = self._stat(stat)
+        t = self._t.get(stat)
+        if t is None:
+            raise ValueError(f"stat {stat!r} was not computed: name it in sliding(..., stats=...) "
+                             f"(this result holds {list(self.stats)})")
+        return t
+
+    def as_batch(self, stat: str = "mean") -> "FleetBatch":
+        """A FleetBatch whose series of this resource is the per-slot ``stat`` (``mean``, ``sum``,
+        ``max`` or ``min``), in HBM as it is: a gapped series over the same offsets, a window with
+        fewer than ``min_count`` present slots being an absent slot.  ``percentile``, ``stats``,
+        ``exceedance`` and ``rollup`` apply to it.  Raises ValueError if an object is flagged
+        KRR_FLAG_NAN: its NaN windows would read as absent and the NaN be dropped."""
+        import torch
+
+        stat = self._stat(stat, _SLIDE_SERIES_STATS)
+        vals = self.tensor(stat)
+        if (self.flags & _native.KRR_FLAG_NAN).any():
+            s = int(np.flatnonzero(self.flags & _native.KRR_FLAG_NAN)[0])
+            raise ValueError(f"object {s} holds a NaN sample (KRR_FLAG_NAN): as a gapped series its NaN windows "
+                             f"would be dropped silently")
+        batch = self._batches.get(stat)
+        if batch is None:
+            longest = int(self.slots.max()) if self.n_objects else 0
+            if vals.is_cuda:
+                ps = PackedSeries(vals.contiguous(), torch.from_numpy(self.offsets).to(vals.device), longest, True)
+            else:
+                ps = PackedSeries(vals.numpy(), self.offsets, longest, True)
+            batch = self._batches[stat] = FleetBatch._of({self.resource: ps}, self.n_objects, self.device,
+                                                         self._engine)
+        return batch
 
 
 _OVERLAY_ALIGN = {"start": _native.KRR_OVERLAY_START, "end": _native.KRR_OVERLAY_END}
@@ -966,6 +1059,67 @@ class FleetBatch:
                                                 r["flags"], r["wcount"], r["min"], r["max"], r["sum"],
                                                 self.device, self.engine)
         return ru
+
+    @staticmethod
+    def _slide_args(window, min_count) -> tuple:
+        cap = _native.KRR_SLIDE_MAX_WINDOW
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+            raise ValueError(f"window must be an int in 1 .. {cap} (slots), got {window!r}")
+        if window > cap:
+            raise ValueError(f"window {window} is above the sliding cap of {cap} slots (KRR_SLIDE_MAX_WINDOW: the "
+                             f"kernel keeps a window in LDS); for coarse windows cut the series with rollup() first "
+                             f"and slide over rollup(...).as_batch('mean')")
+        if min_count is None:
+            min_count = window
+        if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not 1 <= min_count <= window:
+            raise ValueError(f"min_count must be an int in 1 .. window ({window}) or None, got {min_count!r}")
+        return int(window), int(min_count)
+
+    def sliding(self, resource: ResourceType, window: int, min_count: Optional[int] = None,
+                stats: Sequence[str] = ("mean",)) -> FleetSliding:
+        """The moving window over every object's series (FleetSliding): for every slot the
+        ``window`` slots that end there, one krr_segmented_slide pass, cached per (resource,
+        window, min_count, stats).  ``stats`` is a subset of ``mean``, ``sum``, ``max``, ``min``,
+        ``wcount``: each is an array as large as the series, and only those named are allocated
+        and written.  A window is emitted when at least ``min_count`` of its slots are present
+        and is NaN (an absent slot) otherwise; ``min_count=None`` means ``window``: full windows
+        only, as pandas' ``rolling`` does.  A gapped series (scrape failures, pods that came
+        late) usually wants less, or most of its windows are absent: ``min_count=window // 2 + 1``
+        asks for a majority.  The result's ``as_batch(stat)`` is a FleetBatch again:
+
+            batch.sliding(ResourceType.CPU, 5).as_batch("mean").percentile(ResourceType.CPU, "95", mode="linear")
+
+        ``window`` is at most ``KRR_SLIDE_MAX_WINDOW`` slots (a day at 1 minute fits); for coarser
+        windows use ``rollup`` first.  Cost: the window lives in LDS, so long windows run few waves
+        per CU — measured against ``stats`` on the same series, the mean costs 3-4.5x at 5 and 60
+        slots but about 10x at 1,440, and all five stats 6-11x and about 31x (DESIGN.md, k_slide);
+        for a day-long window ``rollup(resource, 60)`` first and a 24-slot slide over the hourly
+        means reads a sixtieth.  Works on a ``per_pod()`` view unchanged (windows per pod).
+        Slides of adjacent time slices cannot be merged (FleetSliding says why)."""
+        window, min_count = self._slide_args(window, min_count)
+        if isinstance(stats, str):
+            stats = (stats,)
+        want = tuple(k for k in _SLIDE_STATS if k in set(stats))
+        if len(want) != len(set(stats)):
+            raise ValueError(f"unknown stat in stats={list(stats)!r}; expected a subset of {list(_SLIDE_STATS)}")
+        resource = ResourceType(resource)
+        key = (resource, "sliding", window, min_count, want)
+        sl = self._cache.get(key)
+        if sl is None:
+            r = self.engine.sliding_series(self.series(resource), window, min_count, want)
+            sl = self._cache[key] = FleetSliding(resource, window, min_count, r["offsets"], r["count"], r["flags"],
+                                                 r["peak"], r["peak_slot"], {k: r[k] for k in want}, self.device,
+                                                 self.engine)
+        return sl
+
+    def sustained_peak(self, resource: ResourceType, window: int, min_count: Optional[int] = None,
+                       return_slot: bool = False):
+        """float64 [S]: the highest mean every object held over ANY ``window`` consecutive slots
+        (NaN without an emitted window, or with a NaN sample) — the launch of ``sliding`` with no
+        per-slot output, so it costs one read of the series.  ``return_slot``: also int64 [S],
+        the first slot such a window ends at (-1 without one).  ``min_count`` as ``sliding``."""
+        sl = self.sliding(resource, window, min_count, stats=())
+        return (sl.peak, sl.peak_slot) if return_slot else sl.peak
 
     def overlay(self, resource: ResourceType, align: str = "end") -> FleetOverlay:
         """Every object's pods folded slot by slot into one series (FleetOverlay): per slot the

@@ -547,6 +547,54 @@ class SimpleEngine:
                                  out["count"], out["flags"])
         return out, wo
 
+    SLIDE_STATS = ("mean", "sum", "max", "min", "wcount")
+
+    def sliding_series(self, ps: PackedSeries, window: int, min_count: int, want=("mean",)) -> dict:
+        """The window of ``window`` slots that ends at every slot of every segment of one series
+        (krr_segmented_slide): for each name in ``want`` (a subset of ``SLIDE_STATS``) a flat
+        DEVICE tensor with one entry per slot, laid out by the series' own offsets — ``mean``,
+        ``sum``, ``max``, ``min`` (float64; NaN where fewer than ``min_count`` slots of the
+        window are present) and ``wcount`` (int32) — each as large as the series, so they stay
+        in HBM and only the ones asked for are allocated and written; ``peak`` (float64: the
+        largest emitted mean), ``peak_slot`` (int64: its first slot, -1 without one), ``count``
+        (int64) and ``flags`` (uint32) as host arrays [S], and ``offsets`` (host int64 [S + 1]).
+        With ``want`` empty the launch reads the series and writes [S] results only.  Chunks as
+        ``stats_series``: whole segments, the chunks' slots concatenated on the device."""
+        import torch
+
+        window, min_count = int(window), int(min_count)
+        want = tuple(k for k in self.SLIDE_STATS if k in set(want))
+        ctx = self.context()  # raises NativeUnavailable without the HIP library or a device
+        dev = torch.device("cuda", self.device)
+        parts = [self._slide_part(ctx, part, window, min_count, want) for part in self._series_parts(ps)]
+        if not parts:
+            res = {k: torch.empty(0, dtype=torch.int32 if k == "wcount" else torch.float64, device=dev) for k in want}
+        elif len(parts) == 1:
+            res = {k: parts[0][k] for k in want}
+        else:
+            res = {k: torch.cat([p[k] for p in parts]) for k in want}
+        seg = {"peak": np.float64, "peak_slot": np.int64, "count": np.int64, "flags": np.int32}
+        res.update(self._host_concat([{k: p[k] for k in seg} for p in parts], seg))
+        offs = ps.offsets if isinstance(ps.offsets, np.ndarray) else ps.offsets.cpu().numpy()
+        res["offsets"] = np.asarray(offs, dtype=np.int64)
+        return res
+
+    def _slide_part(self, ctx, part: PackedSeries, window: int, min_count: int, want: tuple) -> dict:
+        """Upload (host series) and one krr_segmented_slide launch on the current stream: the
+        chunk's device tensors, per-slot ones for the names in ``want`` only."""
+        import torch
+
+        with torch.cuda.device(self.device):
+            series = self._part_series(ctx, part)
+            out = {**self._outputs([(k, torch.int32 if k == "wcount" else torch.float64, 0) for k in want],
+                                   int(series.n_values)),
+                   **self._outputs((("peak", torch.float64, 0), ("peak_slot", torch.int64, 0),
+                                    ("count", torch.int64, 0), ("flags", torch.int32, 0)), part.n_segments)}
+            ctx.segmented_slide(series, window, min_count, out.get("mean"), out.get("sum"), out.get("max"),
+                                out.get("min"), out.get("wcount"), out["peak"], out["peak_slot"], out["count"],
+                                out["flags"])
+        return out
+
     def overlay_series(self, ps: PackedSeries, align: int) -> dict:
         """Every object's pods folded slot by slot (krr_pods_overlay; ``align`` KRR_OVERLAY_START
         or KRR_OVERLAY_END): ``active`` (int32), ``sum``, ``max``, ``min`` (float64) as flat

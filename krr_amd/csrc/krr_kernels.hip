@@ -3989,6 +3989,323 @@ __global__ __launch_bounds__(64) void k_rollup(RollupArgs A) {
     }
 }
 
+// ------------------------------ SLIDE --------------------------------------
+// krr_segmented_slide: the window of W slots that ENDS at every slot (include/krr_amd.h has the
+// rules).  van Herk / Gil-Werman on a grid of W-slot blocks anchored at slot 0: with slot i at
+// position r = i % W of block b, its window is the slots r+1 .. W-1 of block b-1 followed by the
+// slots 0 .. r of block b, so
+//     out(i) = suffix(block b-1, from r+1)  (+)  prefix(block b, to r)
+// for sum, count, min and max alike, and a window's sum adds its own samples only.
+//   - A chunk of the skeleton (1,024 slots in slot order, the head slot in front of the first and
+//     the tail slot behind the last) is written to the LDS `stage` and taken from there in STEPS
+//     of up to 64 consecutive slots, one per lane, that never cross a block boundary.
+//   - A step: an inclusive wave_scan64 over the lanes continues the open block's prefix from a
+//     wave-uniform carry; the lane reads the closed block's suffix at r+1 from LDS (the identity
+//     without a previous block or at r = W-1), combines, stores its outputs and keeps its own
+//     running peak; its raw slot goes to raw[r].
+//   - When a block closes, raw[0, W) is scanned backwards, 64 slots at a time with the lanes
+//     reversed and a carry, into the suffix arrays (sum, packed counts, and min / max when MM).
+// Work per slot is two scan steps whatever W is, but a step never crosses a block boundary, so
+// blocks shorter than a step leave lanes idle.  W <= KRR_SLIDE_DIRECT_MAX therefore takes
+// another kernel (DIRECT): raw[] holds the W - 1 slots before the step and the step's 64 behind
+// them, and every lane folds its own W slots from there, oldest first — no blocks, no scans, W LDS
+// reads per lane and step, the sum in plain slot order.
+// LDS ORDER.  The workgroup is ONE wave, whose DS instructions execute in program order; every
+// hand-over between lanes (stage written -> read, raw written -> scanned, suffix written -> read)
+// has a __syncthreads() between the writes and the reads, which for one wave is the compiler
+// fence plus the wait for the writes (s_waitcnt lgkmcnt(0)) and costs no cross-wave wait.  All
+// branches around them are wave-uniform.
+// Counts are packed as present | poison << 16 (poison: NaN samples of the compact layout); both
+// stay below 2^16 because W <= KRR_SLIDE_MAX_WINDOW.
+constexpr int kSlideStage = 2 * kChunkUnits + 4;  // doubles: [1] head, [2, 1026) the chunk, tail behind it
+#ifndef KRR_SLIDE_DIRECT_MAX
+#define KRR_SLIDE_DIRECT_MAX 24  // windows up to this fold their slots directly (0: every window in blocks);
+                                 // extrapolated from profiles/slide/probe_direct64.json, see DESIGN.md
+#endif
+constexpr int kSlideDirectMax = KRR_SLIDE_DIRECT_MAX;
+static_assert(KRR_SLIDE_MAX_WINDOW < 65536, "packed 16-bit window counts");
+static_assert(8 * kSlideStage + 36 * KRR_SLIDE_MAX_WINDOW <= 65536, "k_slide's LDS at the largest window");
+
+struct SlideArgs {
+    SeriesArgs h;
+    uint32_t W, minc;
+    double* out_mean;  // the five per-slot outputs may each be null
+    double* out_sum;
+    double* out_max;
+    double* out_min;
+    uint32_t* out_cnt;
+    double* out_peak;  // per segment, may be null
+    int64_t* out_pslot;
+};
+
+template <bool MM, bool DIRECT>
+struct SlideProc {
+    double* stage;  // LDS
+    double* raw;
+    double* ssum;
+    double* smin;
+    double* smax;
+    uint32_t* scnt;
+    uint32_t W, minc;
+    uint32_t r;                // position inside the open block of the slot to come
+    bool hasprev, gaps;        // a closed block's suffixes are in LDS
+    double csum, cmin, cmax;   // wave-uniform: the open block's prefix so far
+    uint32_t ccnt;
+    int64_t i0;                // the slot to come
+    int64_t left;              // body slots still to come
+    SegCursor at;
+    bool has_tail, head_pending;
+    double hv;                 // slot 0 of a segment with an odd start
+    uint32_t nans;             // wave-uniform: NaN slots of the segment
+    double best;               // per lane: its largest emitted mean, the first slot with it,
+    int64_t bslot, nslot;      // and its first slot with a NaN mean (-1: none)
+    double* o_mean;            // at the segment's slot 0; null: not written
+    double* o_sum;
+    double* o_max;
+    double* o_min;
+    uint32_t* o_cnt;
+    __device__ __forceinline__ SlideProc(const SegGeom& g, int lane)
+        : left(2 * g.nunits), at(g, lane), has_tail(g.tail), head_pending(g.head) {}
+
+    __device__ __forceinline__ uint32_t pack(bool valid, bool isn) const {
+        return !valid ? 0u : !isn ? 1u : gaps ? 0u : 0x10001u;
+    }
+    __device__ __forceinline__ void open_block() {
+        r = 0u;
+        csum = 0.0;
+        ccnt = 0u;
+        cmin = cmax = bitsd(kQuietNaN);
+    }
+
+    // The block that just filled raw[0, W): its suffixes, from the last 64 slots down.
+    __device__ __forceinline__ void close_block() {
+        __syncthreads();  // raw[] of the steps before
+        double ks = 0.0, kmn = bitsd(kQuietNaN), kmx = bitsd(kQuietNaN);
+        uint32_t kc = 0u;
+        for (int32_t base = (int32_t)((W - 1u) & ~63u); base >= 0; base -= kWave) {
+            const uint32_t idx = (uint32_t)base + (uint32_t)(kWave - 1 - at.lane);  // lane 0: the highest slot
+            const bool valid = idx < W;
+            const double x = valid ? raw[idx] : bitsd(kQuietNaN);
+            const bool isn = __builtin_isnan(x);
+            const double s = bitsd(wave_scan64(dbits(isn ? 0.0 : x), 0ull, OpAddF64Bits{})) + ks;
+            const uint32_t c = wave_scan32(pack(valid, isn), 0u, OpAdd32{}) + kc;
+            if (valid) {
+                ssum[idx] = s;
+                scnt[idx] = c;
+            }
+            ks = bitsd(lane_bcast64(dbits(s), kWave - 1));
+            kc = lane_bcast32(c, kWave - 1);
+            if constexpr (MM) {
+                const double mn = fmin(bitsd(wave_scan64(dbits(x), kQuietNaN, OpMinF64Bits{})), kmn);
+                const double mx = fmax(bitsd(wave_scan64(dbits(x), kQuietNaN, OpMaxF64Bits{})), kmx);
+                if (valid) {
+                    smin[idx] = mn;
+                    smax[idx] = mx;
+                }
+                kmn = bitsd(lane_bcast64(dbits(mn), kWave - 1));
+                kmx = bitsd(lane_bcast64(dbits(mx), kWave - 1));
+            }
+        }
+        __syncthreads();  // the suffixes, before the next step reads them
+        hasprev = true;
+        open_block();
+    }
+
+    // What a lane does with its window once it is folded: tot = packed counts, mn / mx with MM only.
+    __device__ __forceinline__ void finish(bool act, int64_t slot, double sum, uint32_t tot, double mn, double mx) {
+        const double qn = bitsd(kQuietNaN);
+        const uint32_t c = tot & 0xFFFFu;
+        const bool poison = (tot >> 16) != 0u;
+        const bool emitted = act && c >= minc;
+        const bool good = emitted && !poison;
+        double mean = sum / (double)c;
+        sum = good && !__builtin_isnan(sum) ? sum : qn;
+        mean = good && !__builtin_isnan(mean) ? mean : qn;
+        if constexpr (MM) {
+            uint64_t bmn = dbits(mn), bmx = dbits(mx);
+            if (is_zero_bits(bmn)) bmn = 0;
+            if (is_zero_bits(bmx)) bmx = 0;
+            if (!good) bmn = bmx = kQuietNaN;
+            if (act) {
+                if (o_min) o_min[slot] = bitsd(bmn);
+                if (o_max) o_max[slot] = bitsd(bmx);
+            }
+        }
+        if (act) {
+            if (o_mean) o_mean[slot] = mean;
+            if (o_sum) o_sum[slot] = sum;
+            if (o_cnt) o_cnt[slot] = c;
+        }
+        if (emitted) {  // a lane's slots ascend: the first of equal means stays
+            if (__builtin_isnan(mean)) {
+                nslot = nslot < 0 ? slot : nslot;
+            } else if (bslot < 0 || mean > best) {
+                best = mean;
+                bslot = slot;
+            }
+        }
+    }
+
+    // n slots (1..64, wave-uniform, n <= W - r): lane l < n holds slot i0 + l in x, the others a NaN
+    __device__ __forceinline__ void step_blocks(double x, uint32_t n) {
+        const uint32_t lane = (uint32_t)at.lane;
+        const bool act = lane < n;
+        const bool isn = __builtin_isnan(x);
+        const double qn = bitsd(kQuietNaN);
+        nans += popc64(ballot(act && isn));
+        // the open block's prefix to this lane's slot
+        const double ps = csum + bitsd(wave_scan64(dbits(isn ? 0.0 : x), 0ull, OpAddF64Bits{}));
+        const uint32_t pc = ccnt + wave_scan32(pack(act, isn), 0u, OpAdd32{});
+        // the closed block's suffix behind this lane's window start
+        const uint32_t at_r = r + lane + 1u;
+        const bool take = hasprev && act && at_r < W;
+        const uint32_t j = take ? at_r : 0u;
+        const double ss = take ? ssum[j] : 0.0;
+        const uint32_t tot = (take ? scnt[j] : 0u) + pc;
+        double pmn = qn, pmx = qn, mn = qn, mx = qn;
+        if constexpr (MM) {
+            pmn = fmin(cmin, bitsd(wave_scan64(dbits(x), kQuietNaN, OpMinF64Bits{})));
+            pmx = fmax(cmax, bitsd(wave_scan64(dbits(x), kQuietNaN, OpMaxF64Bits{})));
+            mn = fmin(take ? smin[j] : qn, pmn);
+            mx = fmax(take ? smax[j] : qn, pmx);
+        }
+        finish(act, i0 + (int64_t)lane, ss + ps, tot, mn, mx);
+        if (act) raw[r + lane] = x;
+        const int src = (int)n - 1;
+        csum = bitsd(lane_bcast64(dbits(ps), src));
+        ccnt = lane_bcast32(pc, src);
+        if constexpr (MM) {
+            cmin = bitsd(lane_bcast64(dbits(pmn), src));
+            cmax = bitsd(lane_bcast64(dbits(pmx), src));
+        }
+        r += n;
+        i0 += (int64_t)n;
+        if (r == W) close_block();
+    }
+
+    // DIRECT (W <= kSlideDirectMax): raw[0, W-1) holds the W - 1 slots before the step, the step's n
+    // slots (1..64) go behind them, and lane l folds raw[l, l + W) oldest first: a window's sum is
+    // its samples added in slot order.  Slots before the segment's first do not exist: raw[] is never
+    // cleared, and what is stale or unwritten there (the front before a segment's first steps, also
+    // from the segment before; the words read by lanes >= n) is masked by index (`in`) or lane (`act`).
+    __device__ __forceinline__ void step_direct(double x, uint32_t n) {
+        const uint32_t lane = (uint32_t)at.lane;
+        const bool act = lane < n;
+        const double qn = bitsd(kQuietNaN);
+        nans += popc64(ballot(act && __builtin_isnan(x)));
+        if (act) raw[W - 1u + lane] = x;
+        __syncthreads();  // the step's slots, before the lanes after them read
+        const int64_t slot = i0 + (int64_t)lane;
+        const int64_t first = slot - (int64_t)(W - 1u);  // the slot at window position 0
+        double sum = 0.0, mn = qn, mx = qn;
+        uint32_t tot = 0u;
+        for (uint32_t k = 0; k < W; ++k) {
+            const double v = raw[lane + k];
+            const bool in = first + (int64_t)k >= 0;
+            const bool vn = __builtin_isnan(v);
+            sum += in && !vn ? v : 0.0;
+            tot += pack(in, vn);
+            if constexpr (MM) {
+                mn = fmin(mn, in ? v : qn);
+                mx = fmax(mx, in ? v : qn);
+            }
+        }
+        finish(act, slot, sum, tot, mn, mx);
+        // the last W - 1 slots move to the front: read, then write after every lane has read
+        const bool keep = lane + 1u < W;
+        const double moved = keep ? raw[n + lane] : qn;
+        __syncthreads();
+        if (keep) raw[lane] = moved;
+        i0 += (int64_t)n;
+    }
+
+    __device__ __forceinline__ void chunk(const double2 (&c)[kUnroll]) {
+        const bool partial = at.partial();
+        const uint32_t m = (uint32_t)(!partial || left >= 2 * kChunkUnits ? 2 * kChunkUnits : left);  // body slots
+        left -= m;
+        __syncthreads();  // the steps of the chunk before have read their stage
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u)
+            *reinterpret_cast<double2*>(stage + 2 + 2 * kWave * u + 2 * at.lane) = c[u];
+        uint32_t q = 2u, end = 2u + m;
+        if (head_pending) {
+            if (at.lane == 0) stage[1] = hv;
+            q = 1u;
+            head_pending = false;
+        }
+        if (partial && has_tail) {  // the edge unit's .y; after the rows: m = 1022 puts it on that unit's .x
+            if (at.edge(kUnroll - 1)) stage[end] = c[kUnroll - 1].y;
+            ++end;
+        }
+        __syncthreads();  // the stage, before other lanes read it
+        while (q < end) {
+            const uint32_t have = end - q;
+            uint32_t n = have < (uint32_t)kWave ? have : (uint32_t)kWave;
+            if constexpr (!DIRECT) n = n < W - r ? n : W - r;
+            const double x = (uint32_t)at.lane < n ? stage[q + (uint32_t)at.lane] : bitsd(kQuietNaN);
+            if constexpr (DIRECT) step_direct(x, n);
+            else step_blocks(x, n);
+            q += n;
+        }
+        at.next();
+    }
+};
+
+template <bool MM, bool DIRECT>
+__global__ __launch_bounds__(64) void k_slide(SlideArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x;
+    double* const lds = reinterpret_cast<double*>(smem);
+    for (int64_t b = blockIdx.x; b < A.h.S; b += gridDim.x) {
+        const auto [s, beg, end] = series_item(A.h, b);
+        const int64_t L = end > beg ? end - beg : 0;
+        const SegGeom g = seg_geom(beg, end);
+        SlideProc<MM, DIRECT> P(g, lane);
+        P.stage = lds;
+        P.raw = lds + kSlideStage;
+        P.ssum = P.raw + A.W;
+        P.smin = P.ssum + (MM ? A.W : 0u);
+        P.smax = P.smin + (MM ? A.W : 0u);
+        P.scnt = reinterpret_cast<uint32_t*>(P.smax + A.W);
+        P.W = A.W;
+        P.minc = A.minc;
+        P.hasprev = false;
+        P.gaps = A.h.gaps != 0;
+        P.open_block();
+        P.i0 = 0;
+        P.nans = 0u;
+        P.best = bitsd(kQuietNaN);
+        P.bslot = P.nslot = -1;
+        P.o_mean = A.out_mean ? A.out_mean + beg : nullptr;
+        P.o_sum = A.out_sum ? A.out_sum + beg : nullptr;
+        P.o_max = A.out_max ? A.out_max + beg : nullptr;
+        P.o_min = A.out_min ? A.out_min + beg : nullptr;
+        P.o_cnt = A.out_cnt ? A.out_cnt + beg : nullptr;
+        P.hv = g.head ? A.h.vals[beg] : bitsd(kQuietNaN);  // slot 0: the skeleton brings it with the LAST chunk
+        stream_segment<true>(A.h.vals, beg, end, P, lane);
+        // the peak: any NaN mean wins with its first slot, else the largest mean at its first slot
+        const double gmax = wave_max_f64(P.best);
+        const uint64_t fnan = wave_min_u64(P.nslot < 0 ? ~0ull : (uint64_t)P.nslot);
+        const uint64_t fbest = wave_min_u64(P.bslot >= 0 && P.best == gmax ? (uint64_t)P.bslot : ~0ull);
+        uint64_t pk = dbits(gmax);
+        int64_t pslot = (int64_t)fbest;
+        if (is_zero_bits(pk)) pk = 0;
+        if (fnan != ~0ull) {
+            pk = kQuietNaN;
+            pslot = (int64_t)fnan;
+        } else if (fbest == ~0ull) {
+            pk = kQuietNaN;
+            pslot = -1;
+        }
+        const SeriesCount cnt = series_count(A.h, (uint64_t)L, (uint64_t)L - P.nans);
+        if (lane == 0) {
+            if (A.out_peak) A.out_peak[s] = bitsd(pk);
+            if (A.out_pslot) A.out_pslot[s] = pslot;
+            cnt.write(A.h, s);
+        }
+    }
+}
+
 // ------------------------------ OVERLAY ------------------------------------
 // krr_pods_overlay: an object's pods folded slot by slot (include/krr_amd.h has the rules).  One
 // wave per object, no LDS, no atomics.  The lanes lie along the object's slot axis and every lane
@@ -5541,6 +5858,33 @@ int krr_segmented_rollup(krr_ctx* ctx, const krr_series* series, int64_t window,
         const RollupArgs A{H, win_offsets, window, align == KRR_ROLLUP_END, out_wmin, out_wmax, out_wsum, out_wcount};
         if (out_wmin || out_wmax) hipLaunchKernelGGL(k_rollup<true>, grid, dim3(64), 0, (hipStream_t)stream, A);
         else hipLaunchKernelGGL(k_rollup<false>, grid, dim3(64), 0, (hipStream_t)stream, A);
+        return KRR_OK;
+    });
+}
+
+int krr_segmented_slide(krr_ctx* ctx, const krr_series* series, int64_t window, int64_t min_count, double* out_mean,
+                        double* out_sum, double* out_max, double* out_min, uint32_t* out_wcount, double* out_peak,
+                        int64_t* out_peak_slot, int64_t* out_count, uint32_t* out_flags, void* stream) {
+    // a bad window or min_count is an error of an empty series too
+    const int early =
+        window < 1 || window > KRR_SLIDE_MAX_WINDOW
+            ? set_err(ctx, KRR_E_INVALID, "window outside 1..KRR_SLIDE_MAX_WINDOW%s: %lld", "", (long long)window)
+        : min_count < 1 || min_count > window
+            ? set_err(ctx, KRR_E_INVALID, "min_count outside 1..window%s: %lld", "", (long long)min_count)
+            : KRR_OK;
+    return series_entry(ctx, series, out_count, out_flags, early, [&](const SeriesArgs& H, dim3 grid) -> int {
+        if (!out_count || !out_flags) return set_err(ctx, KRR_E_INVALID, "null out_count or out_flags%s", "");
+        const SlideArgs A{H, (uint32_t)window, (uint32_t)min_count, out_mean, out_sum, out_max, out_min, out_wcount,
+                          out_peak, out_peak_slot};
+        const bool mm = out_min || out_max, direct = window <= kSlideDirectMax;
+        // stage, then raw, suffix sums and packed counts, suffix min and max when asked for (<= 64 KiB);
+        // a small window: stage and the W - 1 + 64 raw slots of a step
+        const size_t lds = 8 * (size_t)kSlideStage + (direct ? 8 * (size_t)(window + 63) : (size_t)window * (mm ? 36 : 20));
+        const hipStream_t st = (hipStream_t)stream;
+        if (direct && mm) hipLaunchKernelGGL((k_slide<true, true>), grid, dim3(64), lds, st, A);
+        else if (direct) hipLaunchKernelGGL((k_slide<false, true>), grid, dim3(64), lds, st, A);
+        else if (mm) hipLaunchKernelGGL((k_slide<true, false>), grid, dim3(64), lds, st, A);
+        else hipLaunchKernelGGL((k_slide<false, false>), grid, dim3(64), lds, st, A);
         return KRR_OK;
     });
 }
